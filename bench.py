@@ -28,6 +28,15 @@ Workload = BASELINE.json's metric ("@1080p 8-bounce default scene, 1/2/4/8 GPU")
   --config C3 | C5 select BASELINE configs[2] (256-sphere scene) / configs[4] (glass scene, 32 bounces); --weak grows the
   image with N (~N x 2.07 Mpixel) instead; --strong-4k makes configs[3] the headline workload.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  Everything that takes runs of
+its own moves behind --full: `steady`, `per_frame_launch`, `displayed_frame`, `reference_loop`, `cpu_baseline` (with
+roofline.valu / roofline.secondary, which need its oracle pass), and for N > 1 `in_process_group` and `configs3_4k`.
+
+--dump-outputs DIR writes what the timed path returned after its last step: DIR/result.npy, the float32 (H, W, 4)
+accumulation image (PathTracer.Result; with N > 1 the gathered image).  Above DUMP_LIMIT_BYTES it holds every k-th row, k the
+smallest stride that fits, so that the dump stays within 64 MB.  The inputs are fixed by the arguments (the clock warm-up's
+frames are discarded by ResetRenderer), so two builds can be compared output for output.
+
 The JSON line also carries
   roofline     : the integrator kernel against the HBM roof, from ALGORITHMIC bytes (32 B per pixel per frame: one
                  float4 load + one float4 store of the accumulation image) and the kernel's average duration measured
@@ -190,6 +199,18 @@ def cpu_baseline(pkg, scene, basic, env, width, height, depth, spp, workload_nam
     return out, st["bounces"] / max(1, st["samples"]), st["env_lookups"] / max(1, st["samples"])
 
 
+DUMP_LIMIT_BYTES = 60 << 20  # --dump-outputs: below 64 MB with room for the .npy header
+
+
+def dump_result(directory: str, image: np.ndarray) -> None:
+    """--dump-outputs: DIR/result.npy = every k-th row of `image`, k the smallest stride within DUMP_LIMIT_BYTES (1 at 1080p, 3 at 4K)."""
+    rows, row_bytes, k = image.shape[0], image[0].nbytes, 1
+    while -(-rows // k) * row_bytes > DUMP_LIMIT_BYTES:
+        k += 1
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "result.npy"), np.ascontiguousarray(image[::k], dtype=np.float32))
+
+
 def self_spawn(args) -> int:
     """`python bench.py --gpus N` with no torchrun environment: start the N ranks here (one process per GPU, the same
     environment torchrun would set), pass rank 0's JSON line through, fail if any rank fails or the box has fewer devices."""
@@ -257,13 +278,18 @@ def main():
     ap.add_argument("--strong-4k", action="store_true",
                     help="make BASELINE configs[3] the headline workload: ONE 3840x2160 image row-tiled over the N GPUs")
     ap.add_argument("--weak", action="store_true", help="N > 1: grow the 16:9 image to ~N x 2.07 Mpixel (weak scaling)")
-    ap.add_argument("--no-4k", action="store_true", help="N > 1: skip the extra configs[3] measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (steady state, per-frame launches, displayed frames, the "
+                         "reference's frame loop, the CPU baseline; N > 1: the in-process group check and configs[3] 4K)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's result after its last step to DIR/result.npy (float32, at most 64 MB)")
+    ap.add_argument("--no-4k", action="store_true", help="N > 1, --full: skip the extra configs[3] measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--steady-ms", type=float, default=500.0,
-                    help="after the timed K steps, render the same workload for at least this long in the same process and report it "
-                         "as `steady` (never the metric's value): what a short driver run looks like without its ramp and drain; 0 = off")
+                    help="--full: after the timed K steps, render the same workload for at least this long in the same process and report "
+                         "it as `steady` (never the metric's value): what a short driver run looks like without its ramp and drain; 0 = off")
     ap.add_argument("--no-group-check", action="store_true",
-                    help="N > 1: skip rendering the same frames through ONE in-process group handle (pt_create_multi over the N devices, "
+                    help="N > 1, --full: skip rendering the same frames through ONE in-process group handle (pt_create_multi over the N devices, "
                          "peer copies over xGMI) and comparing it bit for bit with the RCCL-gathered image")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="tuning knob of the library (csrc/pt_tuning.hpp) set through pt_debug_set before any renderer exists, e.g. "
@@ -317,6 +343,7 @@ def main():
     cam = pkg.camera.Camera()
     csrc_hash = pkg.native.csrc_hash()
     frames_per_launch = (args.frame_batch or 64) if args.variant == 0 else 1
+    cpu_baseline_wanted = args.full and world == 1 and not args.no_cpu_baseline
 
     def group_handle_check(W, H, basic, warmup, steps, full):
         """The same W + K frames through ONE in-process pt_create_multi handle over all devices (peer copies over xGMI), compared bit for
@@ -360,9 +387,10 @@ def main():
         gp.Dispose()
         return group
 
-    def measure(W, H, steps, warmup, clock_warmup_ms, steady_ms=0.0, group_check=False):
+    def measure(W, H, steps, warmup, clock_warmup_ms, steady_ms=0.0, group_check=False, keep_result=False):
         """One workload: create the renderer for this rank's rows of the W x H image, warm up, time `steps` Render() calls
-        (barrier + synchronize on both sides, max over ranks), gather once.  -> dict (rank 0) with the raw measurements."""
+        (barrier + synchronize on both sides, max over ranks), gather once.  -> dict (rank 0) with the raw measurements;
+        keep_result: also a host copy of the gathered image as it was after the last timed step ("result")."""
         basic = pkg.camera.basic_data_ubo(cam, W, H)
         pt = pkg.PathTracer(None, W, H, depth, args.spp, 20.0, 0.14, device=local)
         pt.SetVariant(args.variant)
@@ -424,6 +452,8 @@ def main():
         full = gather_image()
         torch.cuda.synchronize()
         present_ms = (time.perf_counter() - t1) * 1e3
+        # (with N = 1 `full` is a view of the bound accumulation buffer, which the --full legs below keep rendering into)
+        result = full.cpu().numpy() if keep_result and rank == 0 else None
 
         times = torch.tensor([elapsed, kernel_ms_total / 1e3], dtype=torch.float64, device="cpu" if args.share_gpu else "cuda")
         if world > 1:
@@ -608,7 +638,7 @@ def main():
                    "devices_used": devices_used, "steady": steady, "per_frame": per_frame, "displayed": displayed, "group": group,
                    "checks": {"finite": bool(torch.isfinite(full).all().item()), "alpha_one": bool((full[..., 3] == 1).all().item()),
                               "mean_radiance": round(float(full[..., :3].mean().item()), 5)},
-                   "basic": basic, "env_cpu": (pt.ReadEnvironment() if env_name != "sky2048" else None),
+                   "result": result, "basic": basic, "env_cpu": (pt.ReadEnvironment() if env_name != "sky2048" and cpu_baseline_wanted else None),
                    # hand-over bound (csrc/pt_kernel_common.hpp): what the repair passes of THIS rank's handle did during the whole run —
                    # all zero unless a launch was abandoned (a contended device)
                    "handover": pkg.native.debug_handover_stats(pt._h)}
@@ -622,9 +652,10 @@ def main():
         (W, H), scaling = weak_image_size(world), "weak"
     else:
         W, H, scaling = 1920, 1080, "strong"  # the metric's image, split N ways (N = 1: the whole image on one GPU)
-    m = measure(W, H, args.steps, args.warmup, args.clock_warmup_ms, steady_ms=args.steady_ms, group_check=not args.no_group_check)
+    m = measure(W, H, args.steps, args.warmup, args.clock_warmup_ms, steady_ms=(args.steady_ms if args.full else 0.0),
+                group_check=args.full and not args.no_group_check, keep_result=args.dump_outputs is not None)
     m4k = None
-    if world > 1 and not (args.strong_4k or args.weak or args.no_4k):
+    if world > 1 and args.full and not (args.strong_4k or args.weak or args.no_4k):
         # BASELINE configs[3]: ONE 3840x2160 image over the N GPUs, same run, shorter (the clocks are warm)
         steps4k = max(64, (args.steps // 4) // 64 * 64)
         m4k = measure(3840, 2160, steps4k, max(64, (args.warmup // 4) // 64 * 64), 0.0)
@@ -739,7 +770,7 @@ def main():
                 "kernel_ms": round(k4, 5), "present_ms": round(m4k["present_ms"], 3), "checks": m4k["checks"],
                 "roofline_frac_hbm": round(a4 / HBM_PEAK_GBS, 5)}
         mean_bounces = miss_fraction = None
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_baseline_wanted:
             env_cpu = m["env_cpu"] if env_name != "sky2048" else pkg.envmap.synthetic_sky_srgb8(2048)
             wl_name = {("default", 8, "atmosphere256"): "C2_default_1080p_d8_atmo"}.get((scene_name, depth, env_name)) if (W, H) == (1920, 1080) and args.spp == 1 else None
             out["cpu_baseline"], mean_bounces, miss_fraction = cpu_baseline(pkg, scene, m["basic"], env_cpu, W, H, depth, args.spp, wl_name)
@@ -761,6 +792,8 @@ def main():
             out["roofline"]["valu"] = {"model_flops_per_sample": round(fl, 1), "mean_bounces": round(mean_bounces, 4),
                                        "achieved": round(tf, 3), "peak": FP32_VALU_PEAK_TF, "unit": "TFLOP/s",
                                        "frac": round(tf / FP32_VALU_PEAK_TF, 4)}
+        if args.dump_outputs is not None:
+            dump_result(args.dump_outputs, m["result"])
         print(json.dumps(out), flush=True)
 
     if world > 1:

@@ -18,6 +18,10 @@ def names(prefix: str) -> list[str]:
 
 def load(name: str) -> dict:
     d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    # an array too large for one committed file continues in NAME.<key>.npy, along its first axis (make_golden.py save)
+    for rest in sorted(glob.glob(os.path.join(GOLDEN, name + ".*.npy"))):
+        key = os.path.basename(rest)[len(name) + 1:-4]
+        d[key] = np.concatenate([d[key], np.load(rest)])
     if "iparams" in d:
         ip, fp = d["iparams"], d["fparams"]
         d.update(width=int(ip[0]), height=int(ip[1]), num_spheres=int(ip[2]), num_cuboids=int(ip[3]), ray_depth=int(ip[4]),

@@ -14,6 +14,7 @@ is appended; the derived text lives only in a temporary file.
 """
 from __future__ import annotations
 
+import glob
 import importlib.util
 import os
 import sys
@@ -32,9 +33,19 @@ spec.loader.exec_module(ref)
 pkg = configs.pkg
 
 
+MAX_FILE_BYTES = 1 << 20  # the limit for one committed file
+
+
 def save(name, **arrays):
     path = os.path.join(HERE, name + ".npz")
+    for stale in glob.glob(os.path.join(HERE, name + ".*.npy")):  # a continuation of an earlier, larger version
+        os.remove(stale)
     np.savez_compressed(path, **arrays)
+    if os.path.getsize(path) > MAX_FILE_BYTES:  # the largest array's second half goes to NAME.<key>.npy (tests/fixtures.py load)
+        key = max(arrays, key=lambda k: arrays[k].nbytes)
+        half = len(arrays[key]) // 2
+        np.save(os.path.join(HERE, f"{name}.{key}.npy"), arrays[key][half:])
+        np.savez_compressed(path, **{**arrays, key: arrays[key][:half]})
     print(f"  wrote {name}.npz ({os.path.getsize(path) / 1024:.1f} KiB)")
 
 

@@ -131,7 +131,7 @@ print(json.dumps({"same": bool((got.view(np.uint32) == want.view(np.uint32)).all
     assert out["plain"]["pairs_repaired"] == 0, out
 
 
-def test_zero_budget_snapshot_presents_are_tone_mapped_again(pkg, native_lib, oracle):
+def test_zero_budget_snapshot_presents_are_tone_mapped_again(pkg, native_lib, oracle, tmp_path):
     """A host that presents every frame through pt_present_rgba8_async (no join between the frame's launch and its tone map): when a
     launch was abandoned, pt_present_wait repairs, tone-maps the snapshot again and copies again — every displayed frame equals the
     post-process of the accumulation image at that frame."""
@@ -142,10 +142,10 @@ def test_zero_budget_snapshot_presents_are_tone_mapped_again(pkg, native_lib, or
     for f in range(w.frames):
         img = oracle.render(w.width, w.height, basic, objs, env, frame_start=f, num_frames=1, image=img, **kw)
         want_frames.append(oracle.postprocess(img)[1].copy())
-    np.save("/tmp/_want_present.npy", np.stack(want_frames))
-    out = _run(r"""
+    want_path = str(tmp_path / "want_present.npy")
+    np.save(want_path, np.stack(want_frames))
+    out = _run(f"want = np.load({want_path!r})\n" + r"""
 w = configs.Workload("present", "default", 256, 144, 8, "sky_f32_32", frames=40)
-want = np.load("/tmp/_want_present.npy")
 pt = make_tracer(pkg, w)
 bad = 0
 # two frames in flight: present frame f into slot f % 3, wait for frame f - 1
@@ -169,7 +169,7 @@ def test_two_processes_on_one_gpu_default_knobs(pkg, native_lib):
     predecessors — about one run in 15 ended in error -5.  With the wall-clock bound and the repair pass the run cannot fail; 6 runs
     here with the library's default knobs (tools/ab/run_2rank.sh repeats it 200 times for profiles/r05)."""
     for i in range(6):
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "64", "--warmup", "64",
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--full", "--steps", "64", "--warmup", "64",
                             "--no-4k", "--steady-ms", "100"], capture_output=True, text=True, timeout=300, cwd=ROOT)
         assert p.returncode == 0, f"run {i}: rc {p.returncode}\n{p.stdout[-1500:]}\n{p.stderr[-3000:]}"
         line = json.loads(p.stdout.strip().splitlines()[-1])

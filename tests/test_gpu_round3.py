@@ -193,7 +193,7 @@ def test_bench_rccl_ranks_over_all_devices(pkg, native_lib):
     n = _device_count(native_lib)
     if n < 2:
         pytest.skip("one HIP device")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "64", "--warmup", "64", "--no-4k",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full", "--steps", "64", "--warmup", "64", "--no-4k",
                         "--steady-ms", "0"], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -212,13 +212,32 @@ def test_bench_self_spawns_ranks_and_refuses_missing_devices(pkg, native_lib):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "64", "--warmup", "64"],
                            capture_output=True, text=True, timeout=300, env=env)
         assert p.returncode != 0 and "refusing" in (p.stderr + p.stdout) and not any(l.startswith("{") for l in p.stdout.splitlines())
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "64", "--warmup", "64", "--no-4k",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--full", "--steps", "64", "--warmup", "64", "--no-4k",
                         "--steady-ms", "100"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["ranks"] == 2 and line["n_gpus"] == 1 and line["checks"]["finite"] and line["steady"]["steps"] >= 512
     # the in-process group handle (here: device 0 twice) rendered the same frames and equals the gathered image of the two ranks
     assert line["in_process_group"].get("error") is None and line["in_process_group"]["equals_rccl_gather_bit_for_bit"] is True
+
+
+def test_bench_plain_run_dumps_the_timed_result(pkg, native_lib, tmp_path):
+    """A plain `bench.py --dump-outputs DIR` runs none of the --full legs and writes the 1080p accumulation image after its last timed
+    step; the same arguments give the same image bit for bit (what lets two builds be compared output for output)."""
+    images = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "4",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 12 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert all(line[k] is None for k in ("steady", "per_frame_launch", "displayed_frame", "reference_loop")) and "cpu_baseline" not in line
+        img = np.load(tmp_path / run / "result.npy")
+        assert img.dtype == np.float32 and img.shape == (1080, 1920, 4)
+        assert np.isfinite(img).all() and (img[..., 3] == 1).all()
+        assert abs(float(img[..., :3].mean(dtype=np.float64)) - line["checks"]["mean_radiance"]) < 1e-4
+        images.append(img)
+    assert np.array_equal(images[0].view(np.uint32), images[1].view(np.uint32))
 
 
 def test_bench_eight_ranks_end_to_end_on_one_gpu(pkg, native_lib):
@@ -228,7 +247,7 @@ def test_bench_eight_ranks_end_to_end_on_one_gpu(pkg, native_lib):
     import time
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--steps", "64", "--warmup", "64",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--full", "--steps", "64", "--warmup", "64",
                         "--steady-ms", "0", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     print(f"8 ranks on one GPU: {time.time() - t0:.1f} s")  # (about 15 s on an idle box; the subprocess is cut off at 10 minutes)

@@ -5,7 +5,7 @@
 #   1. the five real-peer GPU tests (skipped on a one-GPU box): pt_create_multi over distinct devices (peer access is REQUIRED here: a group whose
 #      gather is staged through the host fails the check, pt_multi_gather_is_direct), 1080p over all devices, the hand-over stress on distinct devices, bench.py's self-started
 #      RCCL ranks;
-#   2. bench.py --gpus N for N = 1, 2, 4, 8 (as far as the box has devices), checked per line: n_gpus == ranks == N, finite image with
+#   2. bench.py --gpus N --full for N = 1, 2, 4, 8 (as far as the box has devices), checked per line: n_gpus == ranks == N, finite image with
 #      alpha = 1, in_process_group.equals_rccl_gather_bit_for_bit (N > 1), configs[3] (4K over N) present for N > 1;
 #   3. the N = 1 value against the round's committed BENCH line (profiles/<round>/bench_default.json when present): within 3 %.
 # Exit code 0 only if every step passed.  Writes <out-dir>/multi_gpu_check.json (default gpurun_out/multi_gpu).
@@ -25,7 +25,7 @@ PY
 echo "devices: $N"
 fail=0
 if [ "$DRY" = 1 ]; then
-  timeout 900 python bench.py --gpus 2 --share-gpu --steps 128 --warmup 64 --steady-ms 0 --no-cpu-baseline > "$OUT/bench_g2.json" 2> "$OUT/bench_g2.err" || { echo "FAIL: bench.py --gpus 2 --share-gpu (see $OUT/bench_g2.err)"; fail=1; }
+  timeout 900 python bench.py --gpus 2 --share-gpu --full --steps 128 --warmup 64 --steady-ms 0 --no-cpu-baseline > "$OUT/bench_g2.json" 2> "$OUT/bench_g2.err" || { echo "FAIL: bench.py --gpus 2 --share-gpu (see $OUT/bench_g2.err)"; fail=1; }
 elif [ "$N" -lt 2 ]; then
   echo "this box has $N HIP device(s): the multi-GPU check needs at least 2 (nothing run)"; exit 3
 fi
@@ -35,7 +35,7 @@ tail -n 5 "$OUT/peer_tests.log"
 grep -q "skipped" "$OUT/peer_tests.log" && { echo "FAIL: a real-peer test was skipped on a $N-device box"; fail=1; }
 for n in 1 2 4 8; do
   [ "$n" -gt "$N" ] && continue
-  timeout 1200 python bench.py --gpus $n > "$OUT/bench_g$n.json" 2> "$OUT/bench_g$n.err" || { echo "FAIL: bench.py --gpus $n (see $OUT/bench_g$n.err)"; fail=1; }
+  timeout 1200 python bench.py --gpus $n --full > "$OUT/bench_g$n.json" 2> "$OUT/bench_g$n.err" || { echo "FAIL: bench.py --gpus $n (see $OUT/bench_g$n.err)"; fail=1; }
 done
 fi
 python - "$OUT" "$N" "$DRY" <<'PY' || fail=1

@@ -48,17 +48,18 @@ fi
 
 export TMPDIR=/tmp
 mkdir -p gpurun_out/$RND
+LOG=$_   # the directory made just above: this round's raw output
 timeout 1200 python -m pytest tests -m gpu -q > gpurun_out/$RND/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> gpurun_out/$RND/pytest_gpu.log
 timeout 300 python __graft_entry__.py smoke > gpurun_out/$RND/smoke.log 2>&1
 prof() { local tag=${RND}_$1 key=$2; shift 2
   bash tools/profile_round.sh $tag "$@" > gpurun_out/$RND/${tag}_profile.log 2>&1
   python tools/summarize_profile.py $tag $RND $key ${RND}_default > gpurun_out/$RND/${tag}_summary.log 2>&1
   python bench.py $PROFILE_BENCH_EXTRA "$@" > gpurun_out/$RND/${tag}_bench.json 2> gpurun_out/$RND/${tag}_bench.err; }
-first=1
+first=1; export PROFILE_BENCH_EXTRA=--full   # the recorded bench lines carry every figure of bench.py
 for w in "${MAIN[@]}"; do IFS='|' read tag key args <<< "$w"
   if [ "$tag" = spp4 ] || [ "$tag" = tilewave ]; then export PROFILE_STEPS=192 PROFILE_WARMUP=64; fi
   prof $tag $key $args
-  if [ $first = 1 ]; then first=0; export PROFILE_NO_CAL=1 PROFILE_BENCH_EXTRA="--no-cpu-baseline"; fi   # (calibration + CPU baseline: default workload only)
+  if [ $first = 1 ]; then first=0; export PROFILE_NO_CAL=1 PROFILE_BENCH_EXTRA="--full --no-cpu-baseline"; fi   # (calibration + CPU baseline: default workload only)
 done
 export PROFILE_PASSES="stats fetch write sq" PROFILE_STEPS=256 PROFILE_WARMUP=128
 for w in "${EXTRA[@]}"; do IFS='|' read tag key args <<< "$w"; prof $tag $key $args; done
@@ -90,8 +91,8 @@ python bench.py --steps 20 --warmup 5 > gpurun_out/$RND/driver_command_bench.jso
 python tools/emulate_strong.py gpurun_out/$RND/emulate_strong.json > gpurun_out/$RND/emulate_strong.log 2>&1
 python tools/present_rate.py --json gpurun_out/$RND/present_rate.json > gpurun_out/$RND/present_rate.log 2>&1
 python tools/present_rate.py --devices 0,0 --json gpurun_out/$RND/present_rate_group2.json > gpurun_out/$RND/present_rate_group2.log 2>&1
-python bench.py --gpus 2 --share-gpu --steps 256 --warmup 128 > gpurun_out/$RND/bench_2ranks_one_gpu.json 2> gpurun_out/$RND/bench_2ranks_one_gpu.err
-python bench.py --gpus 8 --share-gpu --steps 64 --warmup 64 --steady-ms 0 > gpurun_out/$RND/bench_8ranks_one_gpu.json 2> gpurun_out/$RND/bench_8ranks_one_gpu.err
+python bench.py --gpus 2 --share-gpu --full --steps 256 --warmup 128 > "$LOG/bench_2ranks_one_gpu.json" 2> "$LOG/bench_2ranks_one_gpu.err"
+python bench.py --gpus 8 --share-gpu --full --steps 64 --warmup 64 --steady-ms 0 > "$LOG/bench_8ranks_one_gpu.json" 2> "$LOG/bench_8ranks_one_gpu.err"
 bash tools/short_runs.sh > gpurun_out/$RND/short_runs.log 2>&1
 bash tools/unchained_timed.sh $RND > gpurun_out/$RND/unchained_timed.log 2>&1
 if [ -x tools/ab/libP.so ]; then for sc in default stress glass; do MI355PT_LIB=$R/tools/ab/libP.so timeout 200 python tools/profile_sections.py $sc 0 640 2>&1 | grep -v amdgpu; done > gpurun_out/$RND/profile_sections.log; fi
