@@ -259,6 +259,16 @@ PT_API int pt_timer_end(pt_handle h, float *out_milliseconds);
  * kernel with k+1 workgroups per CU. */
 PT_API int pt_set_variant(pt_handle h, int variant);
 
+enum { PT_ARITH_CONTRACT = 0, PT_ARITH_REFERENCE = 1 };
+/* Arithmetic of the frames rendered after this call.  CONTRACT (default): the pt-f32 contract, fastest.
+ * REFERENCE: the GL reference's own choices (never fused, correctly rounded / and sqrt, its summation orders
+ * and built-ins) — bit-identical to the reference in ~98.6 % of pixels, several times slower (see DESIGN).
+ * Frames issued before the call keep the arithmetic they were issued under; the accumulation is not reset (call
+ * pt_reset for a clean image).  REFERENCE frames are plain single launches: no frame pipelining, no present
+ * snapshots.  The atmosphere precompute and the post-process stay in contract arithmetic.  Any other mode:
+ * PT_E_BAD_ARGUMENT. */
+PT_API int pt_set_arithmetic(pt_handle h, int mode);
+
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);
 PT_API int pt_device_count(void);

@@ -847,6 +847,16 @@ LaunchMode choose_launch_mode(pt_handle h, pt::FrameArgs &a, int n)
 {
     LaunchMode m;
     m.kernelVariant = h->variant;
+    if (h->arithmetic != PT_ARITH_CONTRACT) { // the reference-arithmetic kernel: one plain launch per frame on the main stream
+        m.chainable = false;
+        m.tagged = false;
+        m.stripes = 1;
+        m.kernelVariant = 1;
+        a.variant = m.kernelVariant;
+        a.drainCompaction = 0;
+        a.tagged = 0;
+        return m;
+    }
     const bool noSingleTagged = pt::tuning().noSingleTagged != 0; // A/B runs
     m.chainable = h->variant == 0 && !h->externalStream() && !ptimpl::timeline_blocks_pipelining(h);
     // (also the first frame of a burst on an idle GPU once the host has pipelined frames before: the batch that follows then chains
@@ -1204,7 +1214,8 @@ int launch_single_stream(pt_handle h, pt::FrameArgs &a, const LaunchMode &m)
     a.queueBase = h->stripeQueueBase[0];
     if (m.tagged) arm_handover(h, a); // (a tagged launch of an A/B variant: alone on the main stream, but its frames still hand pixels over)
     unsigned int tickets = 0;
-    PT_HIP(h, pt::launch_integrate(a, h->stream, &tickets));
+    if (h->arithmetic != PT_ARITH_CONTRACT) PT_HIP(h, pt::launch_integrate_reference(a, h->stream)); // (draws no tickets)
+    else PT_HIP(h, pt::launch_integrate(a, h->stream, &tickets));
     h->stripeQueueBase[0] += tickets; // unsigned wrap-around is fine: the kernel subtracts queueBase modulo 2^32
     hipEvent_t done = ptimpl::next_launch_event(h);
     if (!done) return fail(h, PT_E_HIP, "hipEventCreate failed");
@@ -1323,6 +1334,7 @@ namespace ptimpl {
 // frames one launch may hold for this handle right now (pt_set_frame_batch; automatic: 64, or 256 on a small share)
 int batch_limit(pt_handle h)
 {
+    if (h->arithmetic != PT_ARITH_CONTRACT) return 1; // (the reference-arithmetic kernel renders one frame per launch)
     // (a GPU that owns a small share of the image — fewer than 12,000 tiles per frame, e.g. 1/8 of 1080p — pipelines up to 256 frames
     // per launch when the batch size was left at its default: every launch boundary costs ~0.1 ms of drain + ramp, 7 % of a 64-frame
     // launch there; spp > 1 keeps 64, its kernels carry the frame index in 7 bits)
@@ -1538,7 +1550,7 @@ PT_API int pt_render(pt_handle h, int *out_total_samples)
     // (only the first pt_render after a present is treated that way: a host that goes on rendering without presenting gets
     // its frames pipelined again)
     const bool presentsEveryFrame = h->presentCadence == 1 && h->rendersSincePresent == 0;
-    const bool batchable = h->variant == 0 && h->maxBatch > 1 && !ptimpl::timeline_blocks_pipelining(h) && !h->externalStream() && !presentsEveryFrame;
+    const bool batchable = h->variant == 0 && h->arithmetic == PT_ARITH_CONTRACT && h->maxBatch > 1 && !ptimpl::timeline_blocks_pipelining(h) && !h->externalStream() && !presentsEveryFrame;
     h->rendersSincePresent++;
     h->pendingFrames++;
     h->frame++; // PathTracer.cs:117 post-increment
@@ -1551,7 +1563,7 @@ PT_API int pt_render(pt_handle h, int *out_total_samples)
     // attached: the launch stores the frame's pixels a second time while it resolves them (FrameArgs::snapshot), the present that
     // follows tone-maps that copy, and the tone map never stands between two frames.  (Launched NOW, not by the present: a host
     // that first waits for a present slot and then presents must find the GPU busy.  If no present follows, the copy is ignored.)
-    if (presentsEveryFrame && (h->variant == 0 || h->variant >= 10) && !h->externalStream() && !ptimpl::timeline_blocks_pipelining(h))
+    if (presentsEveryFrame && (h->variant == 0 || h->variant >= 10) && h->arithmetic == PT_ARITH_CONTRACT && !h->externalStream() && !ptimpl::timeline_blocks_pipelining(h))
         return ptimpl::flush_with_snapshot(h, pt::tuning().renderWaitUs);
     // Frames are only held back while the GPU still has integrator work of this handle in flight: deferring can then
     // never idle the device, and a host that leaves time between its frames gets every frame launched at once.
@@ -1718,7 +1730,7 @@ PT_API int pt_present_rgba8_async(pt_handle h, int slot)
         s.inFlight = false;
     }
     s.fedPresent = false;
-    const bool snapshotCapable = (h->variant == 0 || h->variant >= 10) && !h->externalStream() && !ptimpl::timeline_blocks_pipelining(h);
+    const bool snapshotCapable = (h->variant == 0 || h->variant >= 10) && h->arithmetic == PT_ARITH_CONTRACT && !h->externalStream() && !ptimpl::timeline_blocks_pipelining(h);
     if (snapshotCapable && h->pendingFrames > 0)
         if (int rc = ptimpl::flush_with_snapshot(h, pt::tuning().renderWaitUs)) return rc;
     if (snapshotCapable && h->pendingFrames == 0 && h->snapFrame == h->frame && !h->snapLaunches.empty()) {
@@ -2193,6 +2205,18 @@ PT_API int pt_set_variant(pt_handle h, int variant)
     if (int rc = bind_device(h)) return rc;
     if (int rc = join_stripes(h)) return rc; // a different stripe partition must not overlap frames in flight
     h->variant = variant;
+    return PT_OK;
+}
+
+PT_API int pt_set_arithmetic(pt_handle h, int mode)
+{
+    PT_CHECK_HANDLE(h);
+    if (mode != PT_ARITH_CONTRACT && mode != PT_ARITH_REFERENCE) return fail(h, PT_E_BAD_ARGUMENT, "mode must be PT_ARITH_CONTRACT or PT_ARITH_REFERENCE");
+    PT_FAN_OUT(h, pt_set_arithmetic(part, mode));
+    if (int rc = flush_frames(h)) return rc; // pending frames keep the arithmetic they were issued under
+    if (int rc = bind_device(h)) return rc;
+    if (int rc = join_stripes(h)) return rc;
+    h->arithmetic = mode; // (the accumulation is kept, as pt_set_variant keeps it)
     return PT_OK;
 }
 

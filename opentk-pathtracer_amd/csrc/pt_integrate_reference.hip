@@ -1,0 +1,44 @@
+// pt_integrate_reference.hip — the integrator in the REFERENCE arithmetic (pt_set_arithmetic(h, PT_ARITH_REFERENCE); the arithmetic
+// and its specification: pt_math_reference.hpp).  Same shape as variant 1 of pt_integrate_persistent.hip: one wavefront per 8x8 tile,
+// one pixel per lane, the spp loop inside the lane, a plain read-modify-write of the accumulation image with alpha = 1 — no tags, no
+// batching, no snapshot.  The scene is staged into LDS by stage_scene (geometry, materials, sRGB LUT; its 1 / radius table is the
+// contract's and is not read here), and every ray visits all spheres, then all cuboids, in the reference's order.
+// Build flags: those of the library (-ffp-contract=off -fno-fast-math: a written a * b + c keeps two roundings).
+#include "pt_kernel_common.hpp"
+#include "pt_math_reference.hpp"
+
+namespace pt {
+
+__global__ __launch_bounds__(256) void pt_integrate_reference_kernel(const FrameArgs a)
+{
+    SceneLds sc = stage_scene(a);
+    EnvRef env{a.env, (LdsFloats)sc.lut, a.envSize, a.envFormat};
+    const int tid = threadIdx.x;
+    const int b = xcd_band_id(blockIdx.x, gridDim.x);
+    const int wave = tid >> 6, lane = tid & 63;
+    const int tile = b * 4 + wave;
+    if (tile >= a.tilesX * a.tilesY) return;
+    const int tx = tile % a.tilesX, ty = tile / a.tilesX;
+    const int px = tx * 8 + (lane & 7);
+    const int ly = ty * 8 + (lane >> 3); // row inside this launch's row block
+    if (px >= a.width || ly >= a.rows) return;
+    const size_t idx = (size_t)ly * a.width + px;
+    const float4 last = a.accum[idx];                                   // imageLoad  (compute.glsl:126)
+    const float4 next = ref::shade_pixel_ref(a, sc, env, px, global_row(a, ly), last);
+    AUDIT_RESOLVE(a, idx, a.frame, last, next, 1);
+    a.accum[idx] = next;                                                // imageStore (compute.glsl:129)
+}
+
+hipError_t launch_integrate_reference(const FrameArgs &args, hipStream_t stream)
+{
+    FrameArgs a = args;
+    a.materialsInLds = 1; // (stage_scene: materials in LDS, no sphere grid)
+    a.gridLdsBytes = 0;
+    if (a.spp < 1 || a.tilesX < 1 || a.tilesY < 1) return hipErrorInvalidValue;
+    const int tiles = a.tilesX * a.tilesY;
+    const size_t lds = scene_lds_bytes(a.numSpheres, a.numCuboids, a.envFormat, true);
+    hipLaunchKernelGGL(pt_integrate_reference_kernel, dim3((tiles + 3) / 4), dim3(256), lds, stream, a);
+    return hipGetLastError();
+}
+
+} // namespace pt

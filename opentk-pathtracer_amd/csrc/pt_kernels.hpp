@@ -172,6 +172,8 @@ hipError_t launch_integrate(const FrameArgs &a, hipStream_t stream, unsigned int
 // launch order — a no-op unless a.abandonWord says the launch (or one it builds on) was abandoned; then every pixel's missing frames of the
 // launch described by `a` are re-rendered.  ctl = 4 device words (pairs rendered, inconsistent pixels, joins with repairs, spare).
 hipError_t launch_repair(const FrameArgs &a, unsigned int *ctl, hipStream_t stream);
+// the integrator in the reference arithmetic (pt_integrate_reference.hip): one plain frame, one wavefront per 8x8 tile (a.tilesX / a.tilesY set)
+hipError_t launch_integrate_reference(const FrameArgs &a, hipStream_t stream);
 // ... followed by ONE of these: abandon word and ticket counters back to what a fresh chain expects
 hipError_t launch_repair_done(unsigned int *abandonWord, unsigned int *queueMain, unsigned int expectMain, unsigned int *queueChain,
                               unsigned int expectChain, unsigned int *ctl, hipStream_t stream);

@@ -256,6 +256,11 @@ class PathTracer:
     def SetVariant(self, variant: int) -> None:
         check(self._lib.pt_set_variant(self._h, variant), self._h)
 
+    def SetArithmetic(self, mode: int) -> None:
+        """native.PT_ARITH_CONTRACT (default, fastest) or native.PT_ARITH_REFERENCE (the GL reference's own arithmetic: bit-identical to
+        it in ~98.6 % of pixels, slower).  Frames rendered before keep their arithmetic; the accumulation is not reset."""
+        check(self._lib.pt_set_arithmetic(self._h, mode), self._h)
+
     def SetFrameBatch(self, max_frames: int) -> None:
         """Largest number of consecutive Render() calls one launch pipelines (1 = launch every frame at once)."""
         check(self._lib.pt_set_frame_batch(self._h, max_frames), self._h)
