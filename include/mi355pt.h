@@ -265,9 +265,15 @@ enum { PT_ARITH_CONTRACT = 0, PT_ARITH_REFERENCE = 1 };
  * and built-ins) — bit-identical to the reference in ~98.6 % of pixels, several times slower (see DESIGN).
  * Frames issued before the call keep the arithmetic they were issued under; the accumulation is not reset (call
  * pt_reset for a clean image).  REFERENCE frames are plain single launches: no frame pipelining, no present
- * snapshots.  The atmosphere precompute and the post-process stay in contract arithmetic.  Any other mode:
- * PT_E_BAD_ARGUMENT. */
+ * snapshots.  The atmosphere precompute has a switch of its own (pt_atmosphere_set_arithmetic) and is not affected
+ * by this one; the post-process stays in contract arithmetic.  Any other mode: PT_E_BAD_ARGUMENT. */
 PT_API int pt_set_arithmetic(pt_handle h, int mode);
+/* Arithmetic of the pt_atmosphere_render calls that follow (the reference's AtmosphericScatterer is an object of its
+ * own, so is this switch): PT_ARITH_CONTRACT (default) or PT_ARITH_REFERENCE — the GL reference's own choices, within
+ * 1e-4 of its cubes on every texel, at about the same speed (see DESIGN).  The current environment is not touched, nor is
+ * pt_set_arithmetic's mode.  Everything else about pt_atmosphere_render is the same in both modes.  Any other
+ * mode: PT_E_BAD_ARGUMENT, and the previous mode stays in force. */
+PT_API int pt_atmosphere_set_arithmetic(pt_handle h, int mode);
 
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);

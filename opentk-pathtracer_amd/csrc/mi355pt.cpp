@@ -1948,9 +1948,18 @@ PT_API int pt_atmosphere_render(pt_handle h, int size, int i_steps, int j_steps,
     a.iSteps = i_steps;
     a.jSteps = j_steps;
     a.out = (float4 *)h->dEnv;
-    PT_HIP(h, pt::launch_atmosphere(a, h->stream));
+    PT_HIP(h, h->atmoArithmetic == PT_ARITH_REFERENCE ? pt::launch_atmosphere_reference(a, h->stream) : pt::launch_atmosphere(a, h->stream));
     h->envSize = size;
     h->envFormat = PT_ENV_RGBA32F;
+    return PT_OK;
+}
+
+PT_API int pt_atmosphere_set_arithmetic(pt_handle h, int mode)
+{
+    PT_CHECK_HANDLE(h);
+    if (mode != PT_ARITH_CONTRACT && mode != PT_ARITH_REFERENCE) return fail(h, PT_E_BAD_ARGUMENT, "mode must be PT_ARITH_CONTRACT or PT_ARITH_REFERENCE");
+    PT_FAN_OUT(h, pt_atmosphere_set_arithmetic(part, mode));
+    h->atmoArithmetic = mode; // (host state only: the current environment and pending frames are untouched)
     return PT_OK;
 }
 

@@ -3,9 +3,11 @@
 // one pixel per lane, the spp loop inside the lane, a plain read-modify-write of the accumulation image with alpha = 1 — no tags, no
 // batching, no snapshot.  The scene is staged into LDS by stage_scene (geometry, materials, sRGB LUT; its 1 / radius table is the
 // contract's and is not read here), and every ray visits all spheres, then all cuboids, in the reference's order.
+// Also here: the atmosphere precompute in the same arithmetic (atmo_precompute_reference_kernel, at the end).
 // Build flags: those of the library (-ffp-contract=off -fno-fast-math: a written a * b + c keeps two roundings).
 #include "pt_kernel_common.hpp"
 #include "pt_math_reference.hpp"
+#include "pt_atmosphere_reference.hpp"
 
 namespace pt {
 
@@ -38,6 +40,28 @@ hipError_t launch_integrate_reference(const FrameArgs &args, hipStream_t stream)
     const int tiles = a.tilesX * a.tilesY;
     const size_t lds = scene_lds_bytes(a.numSpheres, a.numCuboids, a.envFormat, true);
     hipLaunchKernelGGL(pt_integrate_reference_kernel, dim3((tiles + 3) / 4), dim3(256), lds, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- atmosphere
+// The atmosphere precompute in the reference arithmetic (pt_atmosphere_set_arithmetic; device functions and the x-mirror shortcut
+// with its proof: pt_atmosphere_reference.hpp).  One lane per canonical texel — the lower texel of a mirrored pair or a texel without
+// partner — so the grid holds no idle wavefronts; one wavefront per workgroup (no LDS, no barrier, nothing shared: single wavefronts
+// are the finest grain the dispatcher can spread over the XCDs — a 256^2 cube is 3,092 wavefronts for 1,024 SIMDs).
+__global__ __launch_bounds__(64) void atmo_precompute_reference_kernel(const AtmoArgs a)
+{
+    const int S = a.size;
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= (size_t)S * ref::atmo_row_lanes_ref(S)) return;
+    const ref::AtmoLaneRef o = ref::atmo_lane_ref(a.invProj, &a.invView[0][0], a.lightPos, a.lightIntensity, S, a.iSteps, a.jSteps, i);
+    a.out[o.texel[0]] = make_float4(o.col[0].x, o.col[0].y, o.col[0].z, 1.0f);
+    if (o.n > 1) a.out[o.texel[1]] = make_float4(o.col[1].x, o.col[1].y, o.col[1].z, 1.0f);
+}
+
+hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream)
+{
+    const size_t n = (size_t)a.size * ref::atmo_row_lanes_ref(a.size);
+    hipLaunchKernelGGL(atmo_precompute_reference_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

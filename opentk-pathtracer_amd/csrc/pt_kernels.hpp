@@ -178,6 +178,8 @@ hipError_t launch_integrate_reference(const FrameArgs &a, hipStream_t stream);
 hipError_t launch_repair_done(unsigned int *abandonWord, unsigned int *queueMain, unsigned int expectMain, unsigned int *queueChain,
                               unsigned int expectChain, unsigned int *ctl, hipStream_t stream);
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
+// the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
+hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);
 // masks[kTileMaskWords * tile + w] for every 8x8 tile of the launch described by `a` (tilesX x tilesY tiles; see FrameArgs::tileMasks)
 hipError_t launch_tile_masks(const FrameArgs &a, unsigned long long *masks, hipStream_t stream);
 hipError_t launch_clear(float4 *p, size_t n, hipStream_t stream);

@@ -17,7 +17,8 @@
 //   - sin, cos, exp, pow follow gallivm's algorithms (Mesa lp_bld_arit.c, restated from its published algorithm).
 // With these choices the restatement equals the reference's own output bit for bit in ~98.6 % of the first-frame pixels of the
 // fixtures (the contract: 38.8 %).  Cost: several IEEE divisions per cuboid test (43 issue cycles each on gfx950) — see DESIGN.md.
-// Out of scope (stay in contract arithmetic): the atmosphere precompute and the post-process tone map.
+// The atmosphere precompute in this arithmetic: pt_atmosphere_reference.hpp (a switch of its own, pt_atmosphere_set_arithmetic).
+// Out of scope (stays in contract arithmetic): the post-process tone map.
 //
 // The scalar primitives and vector helpers are __host__ __device__ so that a CPU test can compare them with the oracle bit for bit
 // (that test defines PT_REFERENCE_PRIMITIVES_ONLY: the integrator below needs the device-side scene and environment types).

@@ -66,6 +66,7 @@ struct pt_renderer {
     int frame = 0; // thisRenderNumFrame, PathTracer.cs:113
     int variant = 0;
     int arithmetic = PT_ARITH_CONTRACT; // pt_set_arithmetic: PT_ARITH_REFERENCE renders every frame with pt_integrate_reference_kernel
+    int atmoArithmetic = PT_ARITH_CONTRACT; // pt_atmosphere_set_arithmetic: the kernel of the following pt_atmosphere_render calls
 
     unsigned char basic[PT_BASIC_DATA_UBO_SIZE] = {0};   // host shadow of UBO 0 (travels as kernel argument)
     unsigned char atmoUbo[PT_ATMOSPHERE_UBO_SIZE] = {0}; // host shadow of UBO 2

@@ -385,15 +385,23 @@ public:
         }
     }
     void SetSize(int size) { size_ = size; } // :115-118
+    // PT_ARITH_CONTRACT (default) or PT_ARITH_REFERENCE for the Render() calls that follow (no reference counterpart)
+    void SetArithmetic(int mode)
+    {
+        if (mode != PT_ARITH_CONTRACT && mode != PT_ARITH_REFERENCE) throw std::invalid_argument("AtmosphericScatterer::SetArithmetic: bad mode");
+        arithmetic_ = mode;
+    }
     void Render()                            // :102-113; selects the cube as the tracer's EnvironmentMap (MainWindow.cs:189)
     {
         float a = DegreesToRadians(Time * 360.0f);
         float lightPos[3] = {0.0f * 149600000e3f, std::sin(a) * 149600000e3f, std::cos(a) * 149600000e3f}; // :41
+        Check(pt_atmosphere_set_arithmetic(tracer_.Handle(), arithmetic_), tracer_.Handle());
         Check(pt_atmosphere_render(tracer_.Handle(), size_, ISteps, JSteps, lightPos, std::fmax(LightIntensity, 0.0f)), tracer_.Handle());
     }
 private:
     PathTracer &tracer_;
     int size_;
+    int arithmetic_ = PT_ARITH_CONTRACT;
 };
 
 // ---- MainWindow's scene + camera upload logic (src/MainWindow.cs:131-132,208-267,278-279)

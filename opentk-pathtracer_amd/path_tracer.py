@@ -317,9 +317,18 @@ class AtmosphericScatterer:
         self.LightPos = np.asarray(light_pos, dtype=np.float32)  # from Time, :41
         self._ubo = bytes(atmo_ubo)
         self._tracer = tracer
+        self._arithmetic = native.PT_ARITH_CONTRACT
 
     def SetSize(self, size: int) -> None:  # :115-118
         self.Size = size
+
+    def SetArithmetic(self, mode: int) -> None:
+        """native.PT_ARITH_CONTRACT (default) or native.PT_ARITH_REFERENCE (the GL reference's own arithmetic: every texel within 1e-4
+        of its cube, at about the same speed) for the Render() calls that follow.  Remembered on this object and applied before each Render(), so it
+        survives re-attachment to another tracer; independent of PathTracer.SetArithmetic."""
+        if mode not in (native.PT_ARITH_CONTRACT, native.PT_ARITH_REFERENCE):
+            raise ValueError("mode must be PT_ARITH_CONTRACT or PT_ARITH_REFERENCE")
+        self._arithmetic = mode
 
     def _select(self, tracer: PathTracer) -> None:
         self._tracer = tracer
@@ -332,6 +341,7 @@ class AtmosphericScatterer:
         buf = np.frombuffer(self._ubo, dtype=np.uint8)
         check(t._lib.pt_atmosphere_upload_data(t._h, 0, buf.nbytes, buf.ctypes.data_as(C.c_void_p)), t._h)
         lp = np.ascontiguousarray(self.LightPos, dtype=np.float32)
+        check(t._lib.pt_atmosphere_set_arithmetic(t._h, self._arithmetic), t._h)
         check(t._lib.pt_atmosphere_render(t._h, self.Size, self.ISteps, self.JSteps,
                                           lp.ctypes.data_as(C.POINTER(C.c_float)), max(self.LightIntensity, 0.0)), t._h)
 
