@@ -500,17 +500,21 @@ PT_DEV bool ray_trace_t(const SceneLds &sc, int ns, int nc, v3 o, v3 d, Hit &h, 
     h.T = T;
     h.fromInside = (T == wt2);
     h.nearHitPos = v_fma(d, T, o);
-    if (winner < 256) {
+    // Materials in LDS: one fetch for the whole wavefront.  The sphere and the cuboid lanes differ only in the index, so it is selected
+    // and the four 16-byte reads are issued once, in front of the normals (in each branch they ran twice whenever a wavefront held
+    // winners of both kinds).  Materials in device memory (large scenes) keep one fetch per branch: merged, the 14 registers of the
+    // fetch overlap the cuboid normal, which cost the grid kernels a VGPR spill and one of them a wavefront per SIMD.
+    const bool sphereWon = winner < 256;
+    const int ci = winner - 256;
+    if constexpr (MATLDS) h.m = load_material(sc.mat + 4 * (sphereWon ? winner : ns + ci));
+    if (sphereWon) {
         float4 s = sc.sph[winner];
-        if (MATLDS) h.m = load_material(sc.mat + 4 * winner);
-        else h.m = load_material(sc.objects + 5 * winner + 1); // std140 Sphere = geometry + 4 x float4 material
+        if constexpr (!MATLDS) h.m = load_material(sc.objects + 5 * winner + 1); // std140 Sphere = geometry + 4 x float4 material
         v3 pc = V(h.nearHitPos.x - s.x, h.nearHitPos.y - s.y, h.nearHitPos.z - s.z);
         h.normal = v_scale(pc, sc.invr[winner]); // compute.glsl:316-319; 1/radius = IEEE quotient staged in LDS
     } else {
-        int ci = winner - 256;
         float4 mn = sc.cmin[ci], mx = sc.cmax[ci];
-        if (MATLDS) h.m = load_material(sc.mat + 4 * (ns + ci));
-        else h.m = load_material(sc.objects + 1280 + 6 * ci + 2); // Cuboids[] start at float4 index 1280: min, max, material
+        if constexpr (!MATLDS) h.m = load_material(sc.objects + 1280 + 6 * ci + 2); // Cuboids[] start at float4 index 1280: min, max, material
         h.normal = cuboid_normal(V(mn.x, mn.y, mn.z), V(mx.x, mx.y, mx.z), h.nearHitPos);
     }
     PROF_MARK(3) // winner: material + normal
@@ -696,14 +700,25 @@ PT_DEV unsigned long long cone_cuboid_mask(const SceneLds &sc, int nc, v3 O, flo
 
 // ---------------------------------------------------------------------------------------------- sampling / BSDF
 // compute.glsl:297-307
-PT_DEV v3 cosine_sample_hemisphere(v3 n, uint32_t &seed)
+// in two parts, so that bsdf() can draw for either lobe first and run the direction once: the two draws ...
+PT_DEV void hemisphere_draws(uint32_t &seed, float &z, float &a)
 {
-    float z = f_fma(rand01(seed), 2.0f, -1.0f);
-    float a = rand01(seed) * 2.0f * PI;
+    z = f_fma(rand01(seed), 2.0f, -1.0f);
+    a = rand01(seed) * 2.0f * PI;
+}
+// ... and the direction from (n, z, a)
+PT_DEV v3 hemisphere_direction(v3 n, float z, float a)
+{
     float r = pt_sqrt(f_fma(-z, z, 1.0f));
     float sn, cs;
     pt_sincos(a, sn, cs);
     return v_normalize(v_add(n, V(r * cs, r * sn, z)));
+}
+PT_DEV v3 cosine_sample_hemisphere(v3 n, uint32_t &seed)
+{
+    float z, a;
+    hemisphere_draws(seed, z, a);
+    return hemisphere_direction(n, z, a);
 }
 
 // compute.glsl:359-364
@@ -736,22 +751,35 @@ PT_DEV float bsdf(v3 &ro, v3 &rd, const Hit &h, bool &isRefractive, uint32_t &se
         float diffuse = 1.0f - spec - refr;
         refr = 1.0f - spec - diffuse;
     }
-    v3 diffuseRay = cosine_sample_hemisphere(h.normal, seed);
+    // The reference samples the hemisphere around the normal before it picks the lobe, and around -normal once more inside the
+    // refractive lobe, which uses only the second direction.  A lane therefore needs ONE direction: all draws are taken in the
+    // reference's order (two, the roll, two more on refracting lanes), then the direction is computed once, for whichever
+    // (normal, z, a) the lane ends up with (same arithmetic per lane; one instance of sqrt / sincos / normalize per wave
+    // instead of two whenever any lane refracts).
+    float hz, ha;
+    hemisphere_draws(seed, hz, ha);
     float prob;
     float roll = rand01(seed);
+    const bool specular = spec > roll;
+    const bool refractive = !specular && spec + refr > roll;
+    v3 hn = h.normal;
+    if (refractive) {
+        hemisphere_draws(seed, hz, ha);
+        hn = v_neg(h.normal);
+    }
+    const v3 hemi = hemisphere_direction(hn, hz, ha);
     // the specular and the refractive lobe both end in normalize(mix(...)); the mix is evaluated per lobe and the
     // normalisation once for whichever lobe the lane took (same arithmetic per lane, one code instance per wave)
-    v3 raw = diffuseRay;
+    v3 raw = hemi;
     bool lobe = false;
-    if (spec > roll) {
+    if (specular) {
         v3 refl = f_reflect(rd, h.normal);
-        raw = v_mix(refl, diffuseRay, h.m.specularRoughness * h.m.specularRoughness);
+        raw = v_mix(refl, hemi, h.m.specularRoughness * h.m.specularRoughness);
         prob = spec;
         lobe = true;
-    } else if (spec + refr > roll) {
+    } else if (refractive) {
         v3 rf = f_refract(rd, h.normal, h.fromInside ? h.m.ior : f_rcp(h.m.ior));
-        v3 rough = cosine_sample_hemisphere(v_neg(h.normal), seed);
-        raw = v_mix(rf, rough, h.m.refractionRoughness * h.m.refractionRoughness);
+        raw = v_mix(rf, hemi, h.m.refractionRoughness * h.m.refractionRoughness);
         prob = refr;
         isRefractive = true;
         lobe = true;
@@ -786,6 +814,12 @@ PT_DEV bool bounce_step_t(const SceneLds &sc, int ns, int nc, const EnvRef &env,
         bool isRefractive;
         float prob = bsdf(ro, rd, h, isRefractive, seed);
         PROF_MARK(5) // BSDF
+#ifdef PT_PROFILE
+        // (counted where the wavefront's first lane shades) shading iterations, and those of them in which some lane took the refractive
+        // lobe: the share of iterations that issued bsdf()'s second hemisphere sample before it was merged into the first
+        prof[8] += 1ull;
+        prof[9] += __ballot(isRefractive) != 0ull ? 1ull : 0ull;
+#endif
         rad = V(f_fma(h.m.emissiv.x, throughput.x, rad.x), f_fma(h.m.emissiv.y, throughput.y, rad.y),
                 f_fma(h.m.emissiv.z, throughput.z, rad.z));
         if (!isRefractive) throughput = v_mul(throughput, h.m.albedo);
@@ -819,7 +853,7 @@ PT_DEV bool bounce_step(const SceneLds &sc, int ns, int nc, const EnvRef &env, v
 PT_DEV v3 radiance(const FrameArgs &a, const SceneLds &sc, const EnvRef &env, v3 ro, v3 rd, uint32_t &seed)
 {
 #ifdef PT_PROFILE
-    unsigned long long prof_dummy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long prof_dummy[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     v3 throughput = V(1.0f, 1.0f, 1.0f), rad = V(0.0f, 0.0f, 0.0f);
     for (int i = 0; i < a.rayDepth; i++)

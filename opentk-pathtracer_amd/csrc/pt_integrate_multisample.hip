@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256, 5) void pt_integrate_multisample_kernel(const 
     bool needRay = false, pending = false;
     float walkFrom = -1.0f; // (WALK SLICES, as in the persistent kernel)
 #ifdef PT_PROFILE
-    unsigned long long prof_dummy[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // (this kernel has no section counters of its own)
+    unsigned long long prof_dummy[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // (this kernel has no section counters of its own)
 #endif
     uint32_t seed = 0;
     v3 ro = V(0, 0, 0), rd = V(0, 0, 1), throughput = V(1, 1, 1), rad = V(0, 0, 0);

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void pt_repair_kernel(const FrameArgs a, unsig
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int tiles = a.tilesX * a.tilesY, n = a.batchFrames;
 #ifdef PT_PROFILE
-    unsigned long long prof_dummy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long prof_dummy[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     for (int tile = (int)blockIdx.x * 4 + wave; tile < tiles; tile += (int)gridDim.x * 4) {
         const int tx = tile % a.tilesX, ty = tile / a.tilesX;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void pt_integrate_pool_kernel(const FrameArgs 
     if (next >= poolEnd) return;
 
 #ifdef PT_PROFILE
-    unsigned long long prof_dummy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long prof_dummy[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     // per-lane path state
     int pix = -1;           // linear index into accum, -1 = lane has no pixel
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
     bool exhausted = false;
     bool lastAlive = false;  // this wavefront found itself the last one of its workgroup: it can neither donate nor leave early
 #ifdef PT_PROFILE
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_dummy[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_util[3] = {0, 0, 0};
+    unsigned long long prof[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, prof_dummy[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, prof_util[3] = {0, 0, 0};
     unsigned long long prof_t = __builtin_readcyclecounter();
 #endif
     unsigned long long tStart = 0, tExhausted = 0, nIter = 0;
@@ -1132,6 +1132,7 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
         for (int k = 0; k < 8; k++) {
             atomicAdd(a.timeline + 200000 + k, prof[k]);
             if (k < 3) atomicAdd(a.timeline + 200008 + k, prof_util[k]);
+            if (k < 2) atomicAdd(a.timeline + 200011 + k, prof[8 + k]); // shading iterations, those with a refracting lane (bounce_step_t)
         }
 #endif
     if (TIMELINE && lane == 0) {

@@ -9,6 +9,7 @@
 #      /opt/skills/guides/MI355X_MICROARCH.md prescribes
 # The library batches frames into launches adaptively, so counters are SUMMED over all integrator launches of a run and
 # divided by the frames the run renders (warm-up + timed steps, no clock warm-up).
+# Every pass runs under its own time limit (PROFILE_STEP_TIMEOUT seconds, default 300) and the first one that fails ends the script.
 # Raw output -> gpurun_out/prof_<tag>/ ; tools/summarize_profile.py turns it into the files committed under profiles/.
 export TMPDIR=/tmp
 R=/root/repo
@@ -24,7 +25,8 @@ BENCH="python $R/bench.py --steps $STEPS --warmup $WARM --clock-warmup-ms 0 --st
 CAL="python $R/bench.py --steps $STEPS --warmup $WARM --clock-warmup-ms 0 --steady-ms 0 --no-cpu-baseline --depth 0 ${@:2}"
 # PROFILE_PASSES="stats fetch write sq" restricts the passes (a reduced re-profile after a host-only change); default: all
 run() { name=$1; opts=$2; cmd=$3; if [ -n "$PROFILE_PASSES" ] && [[ " $PROFILE_PASSES " != *" $name "* ]]; then return; fi
-        rocprofv3 --kernel-trace $opts --output-format csv -d $OUT/$name -o $name -- $cmd > $OUT/$name.log 2>&1; }
+        timeout -k 10 ${PROFILE_STEP_TIMEOUT:-300} rocprofv3 --kernel-trace $opts --output-format csv -d $OUT/$name -o $name -- $cmd > $OUT/$name.log 2>&1 ||
+          { echo "profile_round: pass '$name' failed or ran out of time (see $OUT/$name.log): nothing more is started on the GPU"; tail -5 $OUT/$name.log; exit 1; }; }
 run stats "--stats" "$BENCH"
 run fetch "--pmc FETCH_SIZE" "$BENCH"
 run write "--pmc WRITE_SIZE" "$BENCH"
@@ -36,7 +38,7 @@ if [ -z "$PROFILE_NO_CAL" ]; then
   run cal_fetch "--pmc FETCH_SIZE" "$CAL"
   run cal_write "--pmc WRITE_SIZE" "$CAL"
 fi
-python $R/bench.py $PROFILE_BENCH_EXTRA ${@:2} > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 ${PROFILE_STEP_TIMEOUT:-300} python $R/bench.py $PROFILE_BENCH_EXTRA ${@:2} > $OUT/bench.json 2> $OUT/bench.err || { echo "profile_round: bench.py failed"; tail -5 $OUT/bench.err; exit 1; }
 tail -c 400 $OUT/bench.json
 # only the small files travel back (the raw traces are large): per-kernel stats + counter tables, and the integrator's rows of
 # the stats run's kernel trace (start / end of every launch: consecutive launches OVERLAP on two streams, see summarize_profile.py)

@@ -34,6 +34,10 @@ util = buf.reshape(-1)[200008:200011].astype(np.float64) / frames
 if util[0] > 0:
     print(f"generic bounce iterations per frame {util[0]:.0f}, mean active lanes {util[1] / util[0]:.2f} of 64, "
           f"of which waiting for their pixel's previous frame {util[2] / util[0]:.3f}")
+shade = buf.reshape(-1)[200011:200013].astype(np.float64) / frames
+if shade[0] > 0:
+    print(f"generic-bounce shading iterations per frame (sampled where lane 0 shades) {shade[0]:.0f}, of which with a refracting lane "
+          f"{100 * shade[1] / shade[0]:.1f} %")
 names = ["feed (refill/pop/adopt/donate)", "sphere pass", "cuboid pass (+3 rcp)", "winner material+normal", "Beer absorption",
          "BSDF", "tile pass (whole first bounce of a tile)", "RR + resolve + bookkeeping"]
 tot = prof.sum()
