@@ -756,6 +756,11 @@ struct LaunchMode {
     int stripes = 1, kernelVariant = 0;
 };
 
+// Tiles per frame below which a pipelined launch takes 4 tiles per global ticket instead of 8: a small share of an image (a 1/8 share of
+// 1080p has 4,050 tiles per frame for 6,144 wavefronts) then keeps fewer frames in flight at once (+5 % there, neutral above).  (The same
+// number as the carry threshold of plan_launch and Tuning::feedMinTiles, but a decision of its own.)
+constexpr long long kSmallChunkBelowTiles = 12000;
+
 // ---- step 1: inputs -> FrameArgs (everything that does not depend on how the launch reaches the GPU)
 int fill_frame_args(pt_handle h, pt::FrameArgs &a, int firstFrame, int n)
 {
@@ -785,9 +790,8 @@ int fill_frame_args(pt_handle h, pt::FrameArgs &a, int firstFrame, int n)
     a.bandRank = h->bandRank;
     a.localRow0 = 0;
     a.numCUs = h->numCUs;
-    // tiles per global ticket: 8; a pipelined launch over a small share of an image (a 1/8 share of 1080p has 4,050 tiles
-    // per frame for 6,144 wavefronts) takes 4, which keeps fewer frames in flight at once (+5 % there, neutral above)
-    a.queueChunk = h->queueChunk > 0 ? h->queueChunk : (n > 1 && (long long)((h->width + 7) / 8) * ((h->rows + 7) / 8) < 12000 ? 4 : 8);
+    // tiles per global ticket: 8, or 4 for a pipelined launch over a small share of an image (kSmallChunkBelowTiles)
+    a.queueChunk = h->queueChunk > 0 ? h->queueChunk : (n > 1 && (long long)((h->width + 7) / 8) * ((h->rows + 7) / 8) < kSmallChunkBelowTiles ? 4 : 8);
     a.errorWord = h->devErrWord;
     a.startedFlags = nullptr;
     a.launchSeq = 0;
@@ -2165,6 +2169,59 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_build_sphere_grid
     box[9] = g.reach2;
     if (packed && capacity >= (int)g.packed.size() && !g.packed.empty()) std::memcpy(packed, g.packed.data(), g.packed.size());
     return (int)g.packed.size();
+}
+
+// Test aid (not declared in the public header; needs no GPU): what launch_integrate would decide (pt::plan_launch) for a launch with
+// these arguments and these values of the kernel-selection knobs.  The process-wide knobs are not consulted and nothing is launched.
+// kernelRow: the row of the family's dispatch table the plan names (-1: none, or a family without a table).
+// Pointers are only ever tested for null: has* = 1 stands for a non-null one (hasFeed: feed words, display images and display flags).
+struct pt_debug_plan_in {
+    int width, height, tilesX, tilesY, numSpheres, numCuboids, spp, envFormat, variant, batchFrames, tagged, drainCompaction, queueChunk, numCUs,
+        gridBytes, hasGrid, hasTimeline, hasStartedFlags, hasFeed, wantFeed;
+    // pt_tuning.hpp: parked_max, park_capacity, park_min, no_batch_pass, batch_pass_min_tiles, no_sphere_grid, force_lean_lds, carry_last, grid_carry
+    int parkedMax, parkCapacity, parkMin, noBatchPass, batchPassMinTiles, noSphereGrid, forceLeanLds, carryLast, gridCarry;
+};
+struct pt_debug_plan_out {
+    int error, family, kernelRow, minWavesPerSimd, timeline, spp1, matLds, grid, carry, compact, feed, workgroups, ldsBytes, poolTiles;
+    unsigned int ticketsConsumed;
+    int fed;
+    // FrameArgs as the kernel receives it ("set by the launch"); feedSet / displaySet count the non-null feed words and the non-zero display fields
+    int materialsInLds, gridLdsBytes, sceneLdsBytes, parkedMax, contCapacity, contBatchMin, drainCompaction, startedFlagsSet;
+    unsigned int tilesFrameMagic, tilesXMagic;
+    int feedSet, displaySet;
+    // the budget the log_launch line prints
+    int workgroupsPerCU, batchPass, queueLdsBytes, staticLdsBytes, fitPerCU;
+};
+extern "C" __attribute__((visibility("default"))) int pt_debug_plan_launch(const pt_debug_plan_in *in, pt_debug_plan_out *out)
+{
+    if (!in || !out) return PT_E_BAD_ARGUMENT;
+    static unsigned char somewhere[16];
+    pt::FrameArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.width = in->width; a.height = a.rows = in->height; a.tilesX = in->tilesX; a.tilesY = in->tilesY;
+    a.numSpheres = in->numSpheres; a.numCuboids = in->numCuboids; a.spp = in->spp; a.envFormat = in->envFormat; a.variant = in->variant;
+    a.batchFrames = in->batchFrames; a.tagged = in->tagged; a.drainCompaction = in->drainCompaction; a.queueChunk = in->queueChunk;
+    a.numCUs = in->numCUs; a.gridBytes = in->gridBytes;
+    if (in->hasGrid) a.grid = somewhere;
+    if (in->hasTimeline) a.timeline = (unsigned long long *)somewhere;
+    if (in->hasStartedFlags) a.startedFlags = (unsigned int *)somewhere;
+    if (in->hasFeed) {
+        a.feedHost = (const unsigned int *)somewhere; a.feedBcast = (unsigned int *)somewhere; a.feedDone = (unsigned long long *)somewhere;
+        a.displayImages[0] = a.displayImages[1] = a.displayImages[2] = (uchar4 *)somewhere; a.displayPrev = 1; a.displayOn = 1;
+    }
+    pt::Tuning t;
+    t.parkedMax = in->parkedMax; t.parkCapacity = in->parkCapacity; t.parkMin = in->parkMin; t.noBatchPass = in->noBatchPass;
+    t.batchPassMinTiles = in->batchPassMinTiles; t.noSphereGrid = in->noSphereGrid; t.forceLeanLds = in->forceLeanLds; t.carryLast = in->carryLast;
+    t.gridCarry = in->gridCarry;
+    const pt::LaunchPlan p = pt::plan_launch(a, t, in->wantFeed != 0);
+    const pt::FrameArgs &o = p.args;
+    *out = pt_debug_plan_out{(int)p.error, p.family, pt::launch_kernel_row(p), p.kernel.minWavesPerSimd, p.kernel.timeline, p.kernel.spp1, p.kernel.matLds, p.kernel.grid, p.kernel.carry,
+                             p.kernel.compact, p.kernel.feed, p.workgroups, (int)p.ldsBytes, p.poolTiles, p.ticketsConsumed, p.fed, o.materialsInLds, o.gridLdsBytes,
+                             o.sceneLdsBytes, o.parkedMax, o.contCapacity, o.contBatchMin, o.drainCompaction, o.startedFlags != nullptr, o.tilesFrameMagic, o.tilesXMagic,
+                             (o.feedHost != nullptr) + (o.feedBcast != nullptr) + (o.feedDone != nullptr),
+                             (o.displayImages[0] != nullptr) + (o.displayImages[1] != nullptr) + (o.displayImages[2] != nullptr) + (o.displayPrev != 0) + (o.displayOn != 0),
+                             p.workgroupsPerCU, p.batchPass, (int)p.queueLdsBytes, (int)p.staticLdsBytes, p.fitPerCU};
+    return PT_OK;
 }
 
 // Test aid (not declared in the public header): the hand-over audit of the -DPT_AUDIT build.  Drains the handle, then copies up to

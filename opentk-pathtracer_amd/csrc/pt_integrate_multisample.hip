@@ -443,12 +443,18 @@ __global__ __launch_bounds__(256, 5) void pt_integrate_multisample_kernel(const 
     }
 }
 
-hipError_t launch_multisample(const FrameArgs &a, int workgroups, size_t ldsBytes, hipStream_t stream, bool materialsInLds, bool sphereGrid)
+// dispatch table (see kPersistentKernels in pt_integrate_persistent.hip): MIN_WAVES_PER_SIMD = 5 is the kernel's own launch bound
+static const KernelRow kMultisampleKernels[] = {
+    //   timeline, spp1, matLds, grid, carry, compact, feed
+    {{5, false, false, true, false, false, false, false}, pt_integrate_multisample_kernel<true>},
+    {{5, false, false, false, true, false, false, false}, pt_integrate_multisample_kernel<false, true>},
+    {{5, false, false, false, false, false, false, false}, pt_integrate_multisample_kernel<false>},
+};
+
+const KernelRow *multisample_kernels(size_t *count)
 {
-    if (materialsInLds) hipLaunchKernelGGL(pt_integrate_multisample_kernel<true>, dim3(workgroups), dim3(256), ldsBytes, stream, a);
-    else if (sphereGrid) hipLaunchKernelGGL((pt_integrate_multisample_kernel<false, true>), dim3(workgroups), dim3(256), ldsBytes, stream, a);
-    else hipLaunchKernelGGL(pt_integrate_multisample_kernel<false>, dim3(workgroups), dim3(256), ldsBytes, stream, a);
-    return hipGetLastError();
+    *count = sizeof kMultisampleKernels / sizeof kMultisampleKernels[0];
+    return kMultisampleKernels;
 }
 
 } // namespace pt

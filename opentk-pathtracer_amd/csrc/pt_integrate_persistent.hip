@@ -1193,40 +1193,94 @@ static int pool_tiles_for_variant(int variant)
     }
 }
 
-hipError_t launch_integrate(const FrameArgs &args, hipStream_t stream, unsigned int *ticketsConsumed, int *workgroups, bool *fed)
+// ---- the LDS budget plan_launch works with
+// LDS of one CU, and the granule the hardware hands it out in (160 KB / 128) — measured on the 256-sphere scene: 26,880 bytes per
+// workgroup (21 granules) run six workgroups per CU, 27,136 run five, although 6 x 27,136 < 160 KB and
+// hipOccupancyMaxActiveBlocksPerMultiprocessor answers 6 for both.
+constexpr size_t kLdsPerCU = 160 * 1024, kLdsGranule = 1280;
+// static LDS of the persistent kernels per workgroup: queue, drain control; frame-fed: + feed queue, per-wavefront counters
+constexpr size_t kStaticLds = 64, kStaticLdsFed = 256;
+// batch-pass kernel: what a workgroup may take (measured, a 32.3 KB workgroup no longer fits five times into the CU's 160 KB)
+constexpr long long kBatchPassWorkgroupLds = 31ll * 1024;
+// the parked-resolve lists give way before a resident workgroup does, in steps of 8 down to 16 (a list of 16 is plenty on a full-size
+// image; the 256-sphere scene with its grid sits 100 bytes over six workgroups per CU with lists of 64)
+constexpr int kParkedFloor = 16, kParkedStep = 8;
+// tiles per frame from which an image counts as full-size for CARRY (both the plain and the sphere-grid carrying kernel): below, a GPU
+// owns few tiles per frame and the parked resolves are worth more than the carried pixel
+constexpr int kCarryMinTiles = 12000;
+
+// ---- dispatch table of the persistent kernel: every instantiation the library contains, once.  plan_launch names exactly one row
+// (LaunchPlan::kernel); the batch-pass kernel's rows stand beside it (pt_integrate_multisample.hip).
+#ifndef PT_GRID_MIN_WAVES
+#define PT_GRID_MIN_WAVES 6
+#endif
+#ifndef PT_SPP1_WAVES
+#define PT_SPP1_WAVES 6
+#endif
+//                         MIN_WAVES_PER_SIMD, TIMELINE, SPP1, MATLDS, GRID, CARRY, COMPACT, FEED
+#define PT_PERSISTENT_ROW(MW, TL, S1, ML, G, C, CP, F) {{MW, TL, S1, ML, G, C, CP, F}, pt_integrate_persistent_kernel<4, MW, TL, S1, ML, G, C, CP, F>}
+static const KernelRow kPersistentKernels[] = {
+    PT_PERSISTENT_ROW(6, false, true, true, false, true, false, true),                  // frame-fed, the pixel travels with its path
+    PT_PERSISTENT_ROW(6, false, true, true, false, false, false, true),                 // frame-fed
+    PT_PERSISTENT_ROW(PT_SPP1_WAVES, true, true, true, false, false, true, false),      // per-wavefront timestamps (tools/timeline.py)
+    PT_PERSISTENT_ROW(PT_SPP1_WAVES, false, true, true, false, true, false, false),     // the default kernel on full-size images (CARRY)
+    PT_PERSISTENT_ROW(PT_SPP1_WAVES, false, true, true, false, false, false, false),    // tile pass, materials in LDS
+    PT_PERSISTENT_ROW(PT_SPP1_WAVES, false, true, true, false, false, true, false),     // ... with drain compaction
+    PT_PERSISTENT_ROW(PT_GRID_MIN_WAVES, false, true, false, true, true, false, false), // sphere grid, carrying, six workgroups per CU
+    PT_PERSISTENT_ROW(5, false, true, false, true, true, false, false),                 // sphere grid, carrying, five
+    PT_PERSISTENT_ROW(PT_GRID_MIN_WAVES, false, true, false, true, false, false, false), // sphere grid
+    PT_PERSISTENT_ROW(PT_SPP1_WAVES, false, true, false, false, false, true, false),    // tile pass, materials in device memory
+    PT_PERSISTENT_ROW(5, false, false, true, false, false, true, false),                // spp > 1, in-lane sample chain
+    PT_PERSISTENT_ROW(5, false, false, false, true, false, true, false),                // ... sphere grid
+    PT_PERSISTENT_ROW(5, false, false, false, false, false, true, false),               // ... materials in device memory
+};
+#undef PT_PERSISTENT_ROW
+
+// Everything a launch decides, from its arguments and the kernel-selection knobs alone (pt_kernels.hpp: LaunchPlan; no HIP call, no
+// global state, no I/O — tests/test_launch_plan.py calls it through pt_debug_plan_launch on machines without a GPU).  Order of the
+// decisions: family by variant | workgroups per CU | batch pass or sample chain | sphere grid | carry | LDS fit (carry, then the
+// parked lists, then the materials give way) | fed or not | the table row.
+LaunchPlan plan_launch(const FrameArgs &in, const Tuning &tune, bool wantFeed)
 {
-    FrameArgs a = args;
-    const bool wantFeed = fed != nullptr && *fed;
-    if (fed) *fed = false;
+    LaunchPlan p = {};
+    p.error = hipSuccess;
+    FrameArgs &a = p.args;
+    a = in;
     if (!wantFeed) { a.feedHost = nullptr; a.feedBcast = nullptr; a.feedDone = nullptr; a.displayImages[0] = a.displayImages[1] = a.displayImages[2] = nullptr; a.displayPrev = 0; a.displayOn = 0; }
     a.materialsInLds = 1;
     a.gridLdsBytes = 0;
-    *ticketsConsumed = 0;
-    int tiles = a.tilesX * a.tilesY;
+    const int tiles = a.tilesX * a.tilesY;
     a.tilesFrameMagic = div_magic((unsigned int)tiles);
     a.tilesXMagic = div_magic((unsigned int)a.tilesX);
     size_t lds = scene_lds_bytes(a.numSpheres, a.numCuboids, a.envFormat, true);
     if (a.variant == 1) {
-        int nwg = (tiles + 3) / 4;
-        hipLaunchKernelGGL(pt_integrate_kernel, dim3(nwg), dim3(256), lds, stream, a);
+        p.family = kFamilySimple;
+        p.workgroups = (tiles + 3) / 4;
+        p.ldsBytes = lds;
     } else if (a.variant == 0 || a.variant >= 10) {
+        p.family = kFamilyPersistent;
         // 10+k: k+1 workgroups (256 threads) per CU
         const int waves = 4;
         int k = a.variant == 0 ? 4 : a.variant - 10;
         if (k < 0 || k > 7) k = 4;
         int blocksPerCU = k + 1;
         if (a.spp != 1 && blocksPerCU > 5) blocksPerCU = 5; // the kernels without tile pass need 88 VGPRs: 5 wavefronts per SIMD
-        int nwg = a.numCUs * blocksPerCU;
-        if (a.batchFrames < 1 || a.batchFrames > MAX_BATCH_FRAMES) return hipErrorInvalidValue;
+        if (a.batchFrames < 1 || a.batchFrames > MAX_BATCH_FRAMES) {
+            p.error = hipErrorInvalidValue;
+            return p;
+        }
         if (a.batchFrames > 64) a.drainCompaction = 0; // (the drain pool's records keep the frame of the batch in 6 bits)
-        int numChunks = (int)(((long long)tiles * a.batchFrames + a.queueChunk - 1) / a.queueChunk); // (frame, tile) pairs
-        if (nwg > numChunks) nwg = numChunks;
-        if (nwg < 1) nwg = 1;
+        const int numChunks = (int)(((long long)tiles * a.batchFrames + a.queueChunk - 1) / a.queueChunk); // (frame, tile) pairs
+        auto grid_size = [&](int perCU) {
+            int n = a.numCUs * perCU;
+            if (n > numChunks) n = numChunks;
+            return n < 1 ? 1 : n;
+        };
+        int nwg = grid_size(blocksPerCU);
         if (nwg > kStartedWords) a.startedFlags = nullptr; // (the roll call has kStartedWords words; the host then never chains on this launch)
         // Parked resolves (pipelined spp = 1 launches): what a GPU that owns few tiles per frame needs (consecutive frames of a tile in
         // flight together all the time: +20 % at a 1/8 share of 1080p) and a full image does not (+0.3 %).
         a.parkedMax = PARKED_MAX;
-        const Tuning &tune = tuning(); // (pt_tuning.hpp: A/B knobs, set through pt_debug_set only)
         if (tune.parkedMax >= 0) a.parkedMax = tune.parkedMax > PARKED_MAX ? PARKED_MAX : tune.parkedMax;
         const int parkedMaxPlain = a.parkedMax;
         const bool spp1 = a.spp == 1; // tile-pass kernels (the ring holds 60-byte paths instead of 40-byte primary rays)
@@ -1249,8 +1303,7 @@ hipError_t launch_integrate(const FrameArgs &args, hipStream_t stream, unsigned 
         // the continuation queues take what a 5-per-CU workgroup has left next to the scene and the rings (<= 128 entries per wavefront)
         int park = 0;
         if (useBatchPass) {
-            // (31 KB per workgroup: measured, a 32.3 KB workgroup no longer fits five times into the CU's 160 KB)
-            const long long left = 31ll * 1024 - (long long)lds - (long long)waves * 64 * (long long)sizeof(PathEntryM);
+            const long long left = kBatchPassWorkgroupLds - (long long)lds - (long long)waves * 64 * (long long)sizeof(PathEntryM);
             park = (int)(left / (long long)(waves * sizeof(ContEntry))) & ~7;
             if (tune.parkCapacity >= 0) park = tune.parkCapacity & ~7; // A/B runs
             if (park > 128) park = 128;
@@ -1274,14 +1327,12 @@ hipError_t launch_integrate(const FrameArgs &args, hipStream_t stream, unsigned 
         // tiles per frame needs those (+0.3 % at full 1080p); with the sphere grid, or on a small share, the plain kernel stays
         // Sphere-grid scenes (round 5, knob grid_carry): the grid kernel carries the pixel too, at FIVE workgroups per CU (its rings and lane
         // slots need 4.9 KB more than six leave room for; 96 VGPRs instead of 80)
-        const bool gridCarry = useGrid && spp1 && tune.gridCarry != 0 && tiles >= 12000 && tune.carryLast != 0 && a.drainCompaction == 0 && !perWaveTimeline;
+        const bool gridCarry = useGrid && spp1 && tune.gridCarry != 0 && tiles >= kCarryMinTiles && tune.carryLast != 0 && a.drainCompaction == 0 && !perWaveTimeline;
         if (gridCarry && blocksPerCU > 5 && tune.gridCarry == 1) { // (grid_carry = 2: at six workgroups per CU — the 60-byte carried record of round 6 leaves the room)
             blocksPerCU = 5;
-            nwg = a.numCUs * blocksPerCU;
-            if (nwg > numChunks) nwg = numChunks;
-            if (nwg < 1) nwg = 1;
+            nwg = grid_size(blocksPerCU);
         }
-        bool carry = spp1 && (!useGrid || gridCarry) && !perWaveTimeline && tiles >= 12000 && tune.carryLast != 0 && a.drainCompaction == 0;
+        bool carry = spp1 && (!useGrid || gridCarry) && !perWaveTimeline && tiles >= kCarryMinTiles && tune.carryLast != 0 && a.drainCompaction == 0;
         auto queue_bytes = [&](bool c) -> size_t {
             if (useBatchPass) return (size_t)waves * (64 * sizeof(PathEntryM) + (size_t)park * sizeof(ContEntry));
             return (spp1 ? frame_weight_bytes(a.batchFrames) : 0) +
@@ -1289,8 +1340,9 @@ hipError_t launch_integrate(const FrameArgs &args, hipStream_t stream, unsigned 
                    (a.drainCompaction != 0 ? (size_t)pool_slots(waves) * sizeof(PathState) : 0) // no pool without drain compaction
                    + (spp1 && a.tagged && a.drainCompaction == 0 ? (size_t)waves * a.parkedMax * sizeof(ParkedResolve) : 0); // parked resolves of tagged launches
         };
-        // materials leave LDS when they would cost a resident workgroup (160 KB per CU; 64 B of static LDS per workgroup)
-        const size_t ldsPerCU = 160 * 1024, fixedLds = wantFeed ? 256 : 64; // (static LDS of the persistent kernels: queue, drain control; frame-fed: + feed queue, per-wavefront counters)
+        // materials leave LDS when they would cost a resident workgroup
+        const size_t fixedLds = wantFeed ? kStaticLdsFed : kStaticLds;
+        auto fit = [&](size_t bytes) { return kLdsPerCU / ((bytes + fixedLds + kLdsGranule - 1) / kLdsGranule * kLdsGranule); };
         const bool forceLean = tune.forceLeanLds != 0; // A/B runs: materials always from the UBO copy
         size_t queues = 0, ldsTotal = 0;
         a.parkedMax = carry ? 0 : parkedMaxPlain;
@@ -1298,10 +1350,6 @@ hipError_t launch_integrate(const FrameArgs &args, hipStream_t stream, unsigned 
             queues = queue_bytes(carry);
             ldsTotal = lds + queues;
             const size_t ldsLean = scene_lds_bytes(a.numSpheres, a.numCuboids, a.envFormat, false, a.gridLdsBytes) + queues;
-            // The hardware hands out LDS in granules of 1,280 bytes (160 KB / 128) — measured on the 256-sphere scene: 26,880 bytes per
-            // workgroup (21 granules) run six workgroups per CU, 27,136 run five, although 6 x 27,136 < 160 KB and
-            // hipOccupancyMaxActiveBlocksPerMultiprocessor answers 6 for both.
-            auto fit = [&](size_t bytes) { return ldsPerCU / ((bytes + fixedLds + 1279) / 1280 * 1280); };
             size_t wgFull = fit(ldsTotal), wgLean = fit(ldsLean);
             if (wgFull > (size_t)blocksPerCU) wgFull = (size_t)blocksPerCU;
             if (wgLean > (size_t)blocksPerCU) wgLean = (size_t)blocksPerCU;
@@ -1316,11 +1364,9 @@ hipError_t launch_integrate(const FrameArgs &args, hipStream_t stream, unsigned 
                 a.parkedMax = parkedMaxPlain;
                 continue;
             }
-            // the parked-resolve lists give way before a resident workgroup does (a list of 16 is plenty on a full-size image; the 256-sphere
-            // scene with its grid sits 100 bytes over six workgroups per CU with lists of 64)
-            if (!carry && spp1 && a.tagged && a.drainCompaction == 0 && tune.parkedMax < 0 && a.parkedMax > 16 &&
+            if (!carry && spp1 && a.tagged && a.drainCompaction == 0 && tune.parkedMax < 0 && a.parkedMax > kParkedFloor &&
                 (wgFull > wgLean ? wgFull : wgLean) < (size_t)blocksPerCU) {
-                a.parkedMax -= 8;
+                a.parkedMax -= kParkedStep;
                 continue;
             }
             a.materialsInLds = lean ? 0 : 1;
@@ -1328,54 +1374,111 @@ hipError_t launch_integrate(const FrameArgs &args, hipStream_t stream, unsigned 
             break;
         }
         a.sceneLdsBytes = (int)scene_lds_bytes(a.numSpheres, a.numCuboids, a.envFormat, a.materialsInLds != 0, a.gridLdsBytes);
-        if (tuning().logLaunch > 0) {
-            tuning().logLaunch--;
-            std::fprintf(stderr, "mi355pt launch: spp1 %d grid %d carry %d matLds %d batchPass %d frames %d tiles %d wg/CU %d | LDS scene %d + queues %zu = %zu (+%zu static) -> %zu per CU fit, parkedMax %d\n",
-                         (int)spp1, (int)useGrid, (int)carry, a.materialsInLds, (int)useBatchPass, a.batchFrames, tiles, blocksPerCU, a.sceneLdsBytes, queues, ldsTotal, fixedLds,
-                         ldsPerCU / ((ldsTotal + fixedLds + 1279) / 1280 * 1280), a.parkedMax);
-        }
-#ifndef PT_GRID_MIN_WAVES
-#define PT_GRID_MIN_WAVES 6
-#endif
-#ifndef PT_SPP1_WAVES
-#define PT_SPP1_WAVES 6
-#endif
-#define PT_LAUNCH_PERSISTENT(TL, S1, ML) \
-    hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, (S1 ? PT_SPP1_WAVES : 5), TL, S1, ML>), dim3(nwg), dim3(256), ldsTotal, stream, a)
         const bool matLds = a.materialsInLds != 0;
+        p.workgroups = nwg;
+        p.ldsBytes = ldsTotal;
+        p.workgroupsPerCU = blocksPerCU;
+        p.batchPass = useBatchPass;
+        p.queueLdsBytes = queues;
+        p.staticLdsBytes = fixedLds;
+        p.fitPerCU = (int)fit(ldsTotal);
         // frame-fed launch: instantiated for the tile-pass kernels with materials in LDS (the default scene's kernels), five workgroups per CU
         const bool feed = wantFeed && spp1 && matLds && !useGrid && !perWaveTimeline && a.tagged && a.drainCompaction == 0 && blocksPerCU <= 6 &&
                           a.batchFrames == kFeedCapacity && a.feedHost && a.feedBcast && a.feedDone;
-        if (wantFeed && !feed) return hipErrorNotSupported; // (the caller launches the classic way instead; nothing was enqueued)
-        if (feed && carry) hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, 6, false, true, true, false, true, false, true>), dim3(nwg), dim3(256), ldsTotal, stream, a);
-        else if (feed) hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, 6, false, true, true, false, false, false, true>), dim3(nwg), dim3(256), ldsTotal, stream, a);
-        else
-        if (perWaveTimeline && spp1 && matLds) PT_LAUNCH_PERSISTENT(true, true, true); // per-wavefront timestamps (tools/timeline.py)
-        else if (spp1 && matLds && carry) hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, PT_SPP1_WAVES, false, true, true, false, true, false>), dim3(nwg), dim3(256), ldsTotal, stream, a);
-        else if (spp1 && matLds && a.drainCompaction == 0) hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, PT_SPP1_WAVES, false, true, true, false, false, false>), dim3(nwg), dim3(256), ldsTotal, stream, a);
-        else if (spp1 && matLds) PT_LAUNCH_PERSISTENT(false, true, true);
-        else if (spp1 && useGrid && carry && blocksPerCU > 5) hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, PT_GRID_MIN_WAVES, false, true, false, true, true, false>), dim3(nwg), dim3(256), ldsTotal, stream, a);
-        else if (spp1 && useGrid && carry) hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, 5, false, true, false, true, true, false>), dim3(nwg), dim3(256), ldsTotal, stream, a);
-        else if (spp1 && useGrid) hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, PT_GRID_MIN_WAVES, false, true, false, true, false, false>), dim3(nwg), dim3(256), ldsTotal, stream, a);
-        else if (spp1) PT_LAUNCH_PERSISTENT(false, true, false);
-        else if (useBatchPass) (void)launch_multisample(a, nwg, ldsTotal, stream, matLds, useGrid);
-        else if (matLds) PT_LAUNCH_PERSISTENT(false, false, true);
-        else if (useGrid) hipLaunchKernelGGL((pt_integrate_persistent_kernel<4, 5, false, false, false, true>), dim3(nwg), dim3(256), ldsTotal, stream, a);
-        else PT_LAUNCH_PERSISTENT(false, false, false);
-#undef PT_LAUNCH_PERSISTENT
+        if (wantFeed && !feed) p.error = hipErrorNotSupported; // (the caller launches the classic way instead; nothing is enqueued)
+        // The table row.  Flags an instantiation does not have are resolved here (the plain spp = 1 kernel with materials in device memory
+        // is the same whatever carry and drainCompaction say; a grid kernel never has materials in LDS), so the plan names exactly one row.
+        KernelKey &key = p.kernel;
+        key.spp1 = spp1;
+        key.matLds = matLds;
+        key.carry = carry;
+        key.compact = true;
+        if (useBatchPass) {
+            p.family = kFamilyMultisample;
+            key.minWavesPerSimd = 5;
+            key.grid = useGrid;
+            key.compact = false;
+        } else if (feed) {
+            key.minWavesPerSimd = 6;
+            key.compact = false;
+            key.feed = true;
+        } else if (spp1 && matLds) {
+            key.minWavesPerSimd = PT_SPP1_WAVES;
+            key.timeline = perWaveTimeline; // per-wavefront timestamps (tools/timeline.py)
+            key.compact = perWaveTimeline || (!carry && a.drainCompaction != 0);
+        } else if (spp1 && useGrid) {
+            key.minWavesPerSimd = carry && blocksPerCU <= 5 ? 5 : PT_GRID_MIN_WAVES;
+            key.grid = true;
+            key.compact = false;
+        } else if (spp1) {
+            key.minWavesPerSimd = PT_SPP1_WAVES;
+        } else {
+            key.minWavesPerSimd = 5;
+            key.grid = useGrid;
+        }
+        if (p.error != hipSuccess) return p;
         // every workgroup draws tickets until its first failing one: (numChunks - nwg) successful + nwg failing
         // (a pipelined batch draws every chunk dynamically: numChunks successful + nwg failing)
-        *ticketsConsumed = a.tagged ? (unsigned int)(numChunks + nwg) : (unsigned int)(numChunks > nwg ? numChunks : nwg);
+        p.ticketsConsumed = a.tagged ? (unsigned int)(numChunks + nwg) : (unsigned int)(numChunks > nwg ? numChunks : nwg);
         if (feed) { // (the successful tickets depend on how many frames the host publishes: added when it closes the launch)
-            *ticketsConsumed = (unsigned int)nwg;
-            *fed = true;
+            p.ticketsConsumed = (unsigned int)nwg;
+            p.fed = true;
         }
-        if (workgroups) *workgroups = nwg;
     } else {
-        int poolTiles = pool_tiles_for_variant(a.variant);
-        int pools = (tiles + poolTiles - 1) / poolTiles;
-        int nwg = (pools + 3) / 4;
-        hipLaunchKernelGGL(pt_integrate_pool_kernel, dim3(nwg), dim3(256), lds, stream, a, poolTiles);
+        p.family = kFamilyPool;
+        p.poolTiles = pool_tiles_for_variant(a.variant);
+        int pools = (tiles + p.poolTiles - 1) / p.poolTiles;
+        p.workgroups = (pools + 3) / 4;
+        p.ldsBytes = lds;
+    }
+    return p;
+}
+
+static const KernelRow *kernel_table(int family, size_t *count)
+{
+    if (family == kFamilyMultisample) return multisample_kernels(count);
+    *count = family == kFamilyPersistent ? sizeof kPersistentKernels / sizeof kPersistentKernels[0] : 0;
+    return kPersistentKernels;
+}
+
+int launch_kernel_row(const LaunchPlan &p)
+{
+    size_t n = 0;
+    const KernelRow *rows = kernel_table(p.family, &n);
+    for (size_t i = 0; i < n; i++)
+        if (rows[i].key == p.kernel) return (int)i;
+    return -1;
+}
+
+// plan, optionally log, dispatch
+hipError_t launch_integrate(const FrameArgs &args, hipStream_t stream, unsigned int *ticketsConsumed, int *workgroups, bool *fed)
+{
+    const bool wantFeed = fed != nullptr && *fed;
+    const LaunchPlan p = plan_launch(args, tuning(), wantFeed); // (pt_tuning.hpp: A/B knobs, set through pt_debug_set only)
+    const bool queueKernel = p.family == kFamilyPersistent || p.family == kFamilyMultisample;
+    if (fed) *fed = p.fed;
+    *ticketsConsumed = p.ticketsConsumed;
+    if (queueKernel && p.error != hipErrorInvalidValue && tuning().logLaunch > 0) {
+        tuning().logLaunch--;
+        std::fprintf(stderr, "mi355pt launch: spp1 %d grid %d carry %d matLds %d batchPass %d frames %d tiles %d wg/CU %d | LDS scene %d + queues %zu = %zu (+%zu static) -> %zu per CU fit, parkedMax %d\n",
+                     (int)p.kernel.spp1, (int)p.kernel.grid, (int)p.kernel.carry, p.args.materialsInLds, (int)p.batchPass, p.args.batchFrames, p.args.tilesX * p.args.tilesY,
+                     p.workgroupsPerCU, p.args.sceneLdsBytes, p.queueLdsBytes, p.ldsBytes, p.staticLdsBytes, (size_t)p.fitPerCU, p.args.parkedMax);
+    }
+    if (p.error != hipSuccess) return p.error;
+    const dim3 grid(p.workgroups), block(256);
+    if (p.family == kFamilySimple) hipLaunchKernelGGL(pt_integrate_kernel, grid, block, p.ldsBytes, stream, p.args);
+    else if (p.family == kFamilyPool) hipLaunchKernelGGL(pt_integrate_pool_kernel, grid, block, p.ldsBytes, stream, p.args, p.poolTiles);
+    else {
+        const int row = launch_kernel_row(p);
+        if (row < 0) { // (never a neighbouring kernel: every variant renders the same bits, so a wrong row would only show as a speed change)
+            const KernelKey &k = p.kernel;
+            std::fprintf(stderr, "mi355pt launch: no kernel of family %d for minWaves %d timeline %d spp1 %d matLds %d grid %d carry %d compact %d feed %d\n", p.family,
+                         k.minWavesPerSimd, (int)k.timeline, (int)k.spp1, (int)k.matLds, (int)k.grid, (int)k.carry, (int)k.compact, (int)k.feed);
+            return hipErrorInvalidValue;
+        }
+        size_t n = 0;
+        hipLaunchKernelGGL(kernel_table(p.family, &n)[row].entry, grid, block, p.ldsBytes, stream, p.args);
+        if (workgroups) *workgroups = p.workgroups;
     }
     return hipGetLastError();
 }

@@ -443,7 +443,13 @@ struct ContEntry {  // 24 bytes: a pixel between two of its samples
 };
 
 
-// the spp > 1 batch-pass kernel (pt_integrate_multisample.hip), launched by launch_integrate (pt_integrate_persistent.hip)
-hipError_t launch_multisample(const FrameArgs &a, int workgroups, size_t ldsBytes, hipStream_t stream, bool materialsInLds, bool sphereGrid);
+// Dispatch tables: one row per instantiated kernel, (instantiation flags -> entry point).  launch_integrate looks up the row that
+// plan_launch named (LaunchPlan::kernel); a key without a row is an error, never a neighbouring kernel.
+struct KernelRow {
+    KernelKey key;
+    void (*entry)(const FrameArgs);
+};
+// the rows of the spp > 1 batch-pass kernel (pt_integrate_multisample.hip), launched by launch_integrate (pt_integrate_persistent.hip)
+const KernelRow *multisample_kernels(size_t *count);
 
 } // namespace pt

@@ -162,6 +162,49 @@ struct AtmoArgs {
     float4 *out; // [6][size][size]
 };
 
+// ---- Launch plan: everything launch_integrate decides before it enqueues anything, computed by plan_launch — pure host logic
+// (no HIP call, no global state, no I/O), so the decision can be tested without a GPU (pt_debug_plan_launch, tests/test_launch_plan.py).
+enum KernelFamily {
+    kFamilySimple = 0,      // variant 1: one wavefront per 8x8 tile
+    kFamilyPool = 1,        // variants 2..6: wave-local pixel pools
+    kFamilyPersistent = 2,  // variants 0, 10 + k: persistent queue kernel
+    kFamilyMultisample = 3, // ... spp > 1 with the batch pass (pt_integrate_multisample.hip)
+};
+// One instantiation of a queue kernel = one row of its dispatch table (the template arguments, by name)
+struct KernelKey {
+    int minWavesPerSimd;
+    bool timeline, spp1, matLds, grid, carry, compact, feed;
+};
+inline bool operator==(const KernelKey &a, const KernelKey &b)
+{
+    return a.minWavesPerSimd == b.minWavesPerSimd && a.timeline == b.timeline && a.spp1 == b.spp1 && a.matLds == b.matLds && a.grid == b.grid &&
+           a.carry == b.carry && a.compact == b.compact && a.feed == b.feed;
+}
+struct LaunchPlan {
+    hipError_t error;       // hipSuccess, or what launch_integrate returns WITHOUT launching: hipErrorInvalidValue (batchFrames out of range),
+                            // hipErrorNotSupported (a fed launch was asked for and no fed instantiation applies)
+    int family;             // KernelFamily
+    KernelKey kernel;       // persistent / multisample: the table row
+    int workgroups;         // grid size (256 threads each)
+    size_t ldsBytes;        // dynamic LDS per workgroup
+    int poolTiles;          // pool family: tiles per wave-local pool
+    unsigned int ticketsConsumed; // see launch_integrate
+    bool fed;
+    FrameArgs args;         // the kernel argument: the caller's, with every "set by the launch" field filled in (and, for a launch that
+                            // is not fed, the feed and display fields cleared)
+    // persistent / multisample: the LDS budget behind the choice (what log_launch prints)
+    int workgroupsPerCU;
+    bool batchPass;
+    size_t queueLdsBytes, staticLdsBytes;
+    int fitPerCU;           // workgroups of ldsBytes + staticLdsBytes that fit into one CU's LDS
+};
+struct Tuning; // pt_tuning.hpp
+// wantFeed: the caller wants a frame-fed launch (launch_integrate's `fed` on entry)
+LaunchPlan plan_launch(const FrameArgs &in, const Tuning &tune, bool wantFeed);
+// the row of the family's dispatch table that p.kernel names (persistent: kPersistentKernels, multisample: kMultisampleKernels); -1 = none
+int launch_kernel_row(const LaunchPlan &p);
+
+// Plans the launch (plan_launch with the process's knobs), prints the log_launch line when asked to, and dispatches through the kernel tables.
 // ticketsConsumed: by how much the launch advances *a.queue (the caller adds it to the next launch's queueBase)
 // workgroups: the grid size of the launch (persistent kernels)
 // fed (in/out): in = the caller wants a frame-fed launch (a.feedHost etc. set, a.batchFrames = frames published at launch); out = whether one

@@ -37,7 +37,7 @@ struct Tuning {
     long renderWaitUs = 2000;      // ... and the most pt_render itself ever waits (only when the host is 16 launches ahead)
     long handoverBudgetMs = 500;   // hand-over bound: a result that has waited this long (wall clock) for its pixel's previous frame abandons its launch
     long handoverCheckUs = 1000;   // ... and how often a waiting wavefront looks at the abandon word and at its own waits
-    // kernel selection (pt_integrate_persistent.hip: launch_integrate)
+    // kernel selection (pt_integrate_persistent.hip: plan_launch takes them as an argument)
     int parkedMax = -1;            // >= 0: parked resolves per wavefront
     int noBatchPass = 0;           // 1: spp > 1 keeps the in-lane sample chain
     long long batchPassMinTiles = 16384; // pipelined spp > 1 launches over fewer tiles per frame keep the in-lane sample chain
