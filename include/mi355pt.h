@@ -266,7 +266,8 @@ enum { PT_ARITH_CONTRACT = 0, PT_ARITH_REFERENCE = 1 };
  * Frames issued before the call keep the arithmetic they were issued under; the accumulation is not reset (call
  * pt_reset for a clean image).  REFERENCE frames are plain single launches: no frame pipelining, no present
  * snapshots.  The atmosphere precompute has a switch of its own (pt_atmosphere_set_arithmetic) and is not affected
- * by this one; the post-process stays in contract arithmetic.  Any other mode: PT_E_BAD_ARGUMENT. */
+ * by this one, and so has the post-process tone map (pt_present_set_arithmetic): this switch does not select it.
+ * Any other mode: PT_E_BAD_ARGUMENT. */
 PT_API int pt_set_arithmetic(pt_handle h, int mode);
 /* Arithmetic of the pt_atmosphere_render calls that follow (the reference's AtmosphericScatterer is an object of its
  * own, so is this switch): PT_ARITH_CONTRACT (default) or PT_ARITH_REFERENCE — the GL reference's own choices, within
@@ -274,6 +275,23 @@ PT_API int pt_set_arithmetic(pt_handle h, int mode);
  * pt_set_arithmetic's mode.  Everything else about pt_atmosphere_render is the same in both modes.  Any other
  * mode: PT_E_BAD_ARGUMENT, and the previous mode stays in force. */
 PT_API int pt_atmosphere_set_arithmetic(pt_handle h, int mode);
+/* Arithmetic of the tone map (res/shaders/PostProcessing/fragment.glsl:17-44, ScreenEffect.Render) of every present that
+ * follows: pt_present_rgba8, pt_postprocess_device, every path of pt_present_rgba8_async (snapshot, row stripes,
+ * accumulation image; slots bound with pt_present_bind_device_image included) and the per-device pass of a group handle
+ * before its gather.  PT_ARITH_CONTRACT (default) or PT_ARITH_REFERENCE — the GL reference's own choices: multiply-adds
+ * with two roundings, a true division, IEEE min / max for the clamp, its pow with the exponent (float)(1 / 2.4), and the
+ * final mix(.., lessThan(..)) as a SELECT between v * 12.92 and the power branch; the float colour is then bit-identical
+ * to the reference's on all 18,432 values of its fixture (see DESIGN).  The same in both modes: float -> unorm8 is
+ * round-half-up of clamp(v, 0, 1) * 255 (the reference's fixture holds the shader's float colour only), a NaN colour is
+ * clamped by IEEE minNum / maxNum and so becomes 0 (as do NaN and +-inf inputs; the reference's data holds none), alpha
+ * is 255.  A switch of its own: it touches neither pt_set_arithmetic's nor pt_atmosphere_set_arithmetic's mode, nor the
+ * accumulation image, the frame counter or the environment, and it fans out to every part of a group handle.  A call
+ * that CHANGES the mode first launches what is pending and closes an open frame-fed launch (a call with the mode in
+ * force does nothing and costs nothing, so a host may make it every frame); a present already in flight keeps the
+ * arithmetic it was issued under.  While the mode is REFERENCE, a host that presents every frame into bound device images gets
+ * snapshot or per-frame presents instead of the display fused into the frame-fed launch (that one is the contract's tone
+ * map).  Any other mode: PT_E_BAD_ARGUMENT, and the previous mode stays in force. */
+PT_API int pt_present_set_arithmetic(pt_handle h, int mode);
 
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);

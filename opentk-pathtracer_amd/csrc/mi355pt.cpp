@@ -186,7 +186,7 @@ static int resolve_fused_orphan(pt_handle h)
     if (!s.fusedWaiting) return PT_OK;
     void *const image = s.boundDev ? s.boundDev : s.dRgba8;
     const size_t pixels = (size_t)s.rows * s.width;
-    PT_HIP(h, pt::launch_postprocess(h->accum(), image, pixels, h->stream));
+    PT_HIP(h, ptimpl::launch_tone_map(s.arithmetic, h->accum(), image, pixels, h->stream));
     PT_HIP(h, hipEventRecord(s.toneMapped, h->stream));
     PT_HIP(h, hipStreamWaitEvent(h->copyStream, s.toneMapped, 0));
     if (!s.boundDev) PT_HIP(h, hipMemcpyAsync(s.host, s.dRgba8, pixels * 4, hipMemcpyDeviceToHost, h->copyStream));
@@ -1000,7 +1000,9 @@ bool feed_wanted(pt_handle h, const pt::FrameArgs &a, int n, bool lastOfFlush)
         // stays on the device (pt_present_bind_device_image: the interop-style present).  A slot with a host image needs the runtime's copy
         // kernel per frame, which finds no room beside resident wavefronts (measured: it ran when the launch ended) and is PCIe-bound
         // anyway (0.157 ms per 1080p frame): such hosts keep the per-frame launches.
-        if (pt::tuning().feedDisplay == 0 || n != 1 || !h->lastPresentBound) return false;
+        // The fused display is the CONTRACT tone map (display_pixel in pt_integrate_persistent.hip): a handle whose presents are in the
+        // reference arithmetic (pt_present_set_arithmetic) keeps the snapshot / per-frame presents, which launch the kernel of its choice.
+        if (pt::tuning().feedDisplay == 0 || n != 1 || !h->lastPresentBound || h->presentArithmetic != PT_ARITH_CONTRACT) return false;
         for (const ptimpl::PresentSlot &s : h->slots)
             if (s.boundDev && s.boundBytes < h->tilePixels() * 4) return false;
     }
@@ -1384,7 +1386,7 @@ int flush_frames(pt_handle h) { return flush_frames_bounded(h, pt::tuning().chai
 int tone_map_into(pt_handle h, void *dst)
 {
     if (int rc = join_stripes(h)) return rc;
-    PT_HIP(h, pt::launch_postprocess(h->accum(), dst, h->tilePixels(), h->stream));
+    PT_HIP(h, ptimpl::launch_tone_map(h->presentArithmetic, h->accum(), dst, h->tilePixels(), h->stream));
     return PT_OK;
 }
 
@@ -1719,6 +1721,7 @@ PT_API int pt_present_rgba8_async(pt_handle h, int slot)
             s.frame = h->frame;
             s.rows = h->rows;
             s.width = h->width;
+            s.arithmetic = h->presentArithmetic; // (PT_ARITH_CONTRACT: feed_wanted opens no displaying launch otherwise)
             s.snapSource = image; // (non-null: pt_present_wait looks at the abandon epoch)
             s.snapGeneration = 0;
             s.abandonEpoch = h->abandonEpoch;
@@ -1751,7 +1754,7 @@ PT_API int pt_present_rgba8_async(pt_handle h, int slot)
             if (s.inFlight && hipEventQuery(s.copied) != hipSuccess) PT_HIP(h, hipEventSynchronize(s.copied));
             (void)hipGetLastError(); // (hipErrorNotReady of the query is not an error)
             for (const pt_renderer::SnapLaunch &l : h->snapLaunches) {
-                PT_HIP(h, pt::launch_postprocess(h->dSnap[k] + l.firstPixel, (char *)image + l.firstPixel * 4, l.pixels, l.stream));
+                PT_HIP(h, ptimpl::launch_tone_map(h->presentArithmetic, h->dSnap[k] + l.firstPixel, (char *)image + l.firstPixel * 4, l.pixels, l.stream));
                 PT_HIP(h, hipEventRecord(l.done, l.stream)); // "launch done" now includes its tone map
                 PT_HIP(h, hipStreamWaitEvent(h->copyStream, l.done, 0));
             }
@@ -1764,6 +1767,7 @@ PT_API int pt_present_rgba8_async(pt_handle h, int slot)
             s.frame = h->frame;
             s.rows = h->rows;
             s.width = h->width;
+            s.arithmetic = h->presentArithmetic;
             s.snapSource = h->dSnap[k];
             s.snapGeneration = h->snapGeneration[k];
             s.abandonEpoch = h->abandonEpoch;
@@ -1787,14 +1791,14 @@ PT_API int pt_present_rgba8_async(pt_handle h, int slot)
             hipStream_t st = ptimpl::stripe_stream(h, j);
             if (s.inFlight) PT_HIP(h, hipStreamWaitEvent(st, s.copied, 0));
             const size_t first = (size_t)h->stripeRow0[j] * h->width, count = (size_t)h->stripeRows[j] * h->width;
-            PT_HIP(h, pt::launch_postprocess(h->accum() + first, (char *)image + first * 4, count, st));
+            PT_HIP(h, ptimpl::launch_tone_map(h->presentArithmetic, h->accum() + first, (char *)image + first * 4, count, st));
             PT_HIP(h, hipEventRecord(h->stripeDone[j], st)); // "stripe done" now includes its tone map
             PT_HIP(h, hipStreamWaitEvent(h->copyStream, h->stripeDone[j], 0));
         }
     } else {
         if (int rc = join_stripes(h)) return rc;
         if (s.inFlight) PT_HIP(h, hipStreamWaitEvent(h->stream, s.copied, 0));
-        PT_HIP(h, pt::launch_postprocess(h->accum(), image, pixels, h->stream));
+        PT_HIP(h, ptimpl::launch_tone_map(h->presentArithmetic, h->accum(), image, pixels, h->stream));
         PT_HIP(h, hipEventRecord(s.toneMapped, h->stream));
         // later frames only wait for the tone-map pass (stream order); the PCIe copy runs beside them on the copy stream
         PT_HIP(h, hipStreamWaitEvent(h->copyStream, s.toneMapped, 0));
@@ -1806,6 +1810,7 @@ PT_API int pt_present_rgba8_async(pt_handle h, int slot)
     s.frame = h->frame;
     s.rows = h->rows;
     s.width = h->width;
+    s.arithmetic = h->presentArithmetic;
     s.snapSource = nullptr; // (tone-mapped from the accumulation image behind a join: the repair passes ran in front of it)
     return PT_OK;
 }
@@ -1865,7 +1870,7 @@ PT_API int pt_present_wait(pt_handle h, int slot, const uint8_t **out_host_rgba8
                 if (int rc = ptimpl::fix_alpha(h)) return rc;
                 void *const image = s.boundDev ? s.boundDev : s.dRgba8;
                 const size_t pixels = (size_t)s.rows * s.width;
-                PT_HIP(h, pt::launch_postprocess(h->accum(), image, pixels, h->stream));
+                PT_HIP(h, ptimpl::launch_tone_map(s.arithmetic, h->accum(), image, pixels, h->stream));
                 if (!s.boundDev) PT_HIP(h, hipMemcpyAsync(s.host, s.dRgba8, pixels * 4, hipMemcpyDeviceToHost, h->stream));
                 PT_HIP(h, hipStreamSynchronize(h->stream));
                 if (int rc = ptimpl::settle_handover(h)) return rc;
@@ -1880,7 +1885,7 @@ PT_API int pt_present_wait(pt_handle h, int slot, const uint8_t **out_host_rgba8
                 if (int rc = join_stripes(h)) return rc;
                 void *const image = s.boundDev ? s.boundDev : s.dRgba8;
                 const size_t pixels = (size_t)s.rows * s.width;
-                PT_HIP(h, pt::launch_postprocess(h->dSnap[k], image, pixels, h->stream));
+                PT_HIP(h, ptimpl::launch_tone_map(s.arithmetic, h->dSnap[k], image, pixels, h->stream));
                 if (!s.boundDev) PT_HIP(h, hipMemcpyAsync(s.host, s.dRgba8, pixels * 4, hipMemcpyDeviceToHost, h->stream));
                 PT_HIP(h, hipStreamSynchronize(h->stream));
                 s.abandonEpoch = h->abandonEpoch;
@@ -1964,6 +1969,20 @@ PT_API int pt_atmosphere_set_arithmetic(pt_handle h, int mode)
     if (mode != PT_ARITH_CONTRACT && mode != PT_ARITH_REFERENCE) return fail(h, PT_E_BAD_ARGUMENT, "mode must be PT_ARITH_CONTRACT or PT_ARITH_REFERENCE");
     PT_FAN_OUT(h, pt_atmosphere_set_arithmetic(part, mode));
     h->atmoArithmetic = mode; // (host state only: the current environment and pending frames are untouched)
+    return PT_OK;
+}
+
+PT_API int pt_present_set_arithmetic(pt_handle h, int mode)
+{
+    PT_CHECK_HANDLE(h);
+    if (mode != PT_ARITH_CONTRACT && mode != PT_ARITH_REFERENCE) return fail(h, PT_E_BAD_ARGUMENT, "mode must be PT_ARITH_CONTRACT or PT_ARITH_REFERENCE");
+    PT_FAN_OUT(h, pt_present_set_arithmetic(part, mode));
+    if (mode == h->presentArithmetic) return PT_OK; // (a host that sets the mode every frame keeps its pipelining: nothing to order)
+    if (int rc = bind_device(h)) return rc;
+    // pending frames are launched and an open frame-fed launch is closed: a present it still owes (fused display) is tone-mapped in the
+    // arithmetic it was issued under (PresentSlot::arithmetic), and no displaying launch stays open across the switch (feed_wanted)
+    if (int rc = join_stripes(h)) return rc;
+    h->presentArithmetic = mode; // (the accumulation image, the frame counter, the environment and the two other switches are untouched)
     return PT_OK;
 }
 

@@ -269,7 +269,7 @@ int group_present_async(pt_handle g, int slot)
         if (int rc = ptimpl::join_stripes(p)) return part_fail(g, p, rc);
         // the root's previous pull from this part's slot image must have finished before it is overwritten
         if (gs.inFlight) PT_HIP(g, hipStreamWaitEvent(p->stream, gs.copied, 0));
-        PT_HIP(g, pt::launch_postprocess(p->accum(), ps.dRgba8, p->tilePixels(), p->stream));
+        PT_HIP(g, ptimpl::launch_tone_map(p->presentArithmetic, p->accum(), ps.dRgba8, p->tilePixels(), p->stream));
         PT_HIP(g, hipEventRecord(ps.toneMapped, p->stream));
         src.push_back(ps.dRgba8);
         ready.push_back(ps.toneMapped);

@@ -3,11 +3,13 @@
 // one pixel per lane, the spp loop inside the lane, a plain read-modify-write of the accumulation image with alpha = 1 — no tags, no
 // batching, no snapshot.  The scene is staged into LDS by stage_scene (geometry, materials, sRGB LUT; its 1 / radius table is the
 // contract's and is not read here), and every ray visits all spheres, then all cuboids, in the reference's order.
-// Also here: the atmosphere precompute in the same arithmetic (atmo_precompute_reference_kernel, at the end).
+// Also here: the atmosphere precompute (atmo_precompute_reference_kernel) and the post-process tone map (pt_postprocess_reference_kernel)
+// in the same arithmetic, at the end.
 // Build flags: those of the library (-ffp-contract=off -fno-fast-math: a written a * b + c keeps two roundings).
 #include "pt_kernel_common.hpp"
 #include "pt_math_reference.hpp"
 #include "pt_atmosphere_reference.hpp"
+#include "pt_postprocess_reference.hpp"
 
 namespace pt {
 
@@ -62,6 +64,28 @@ hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream)
 {
     const size_t n = (size_t)a.size * ref::atmo_row_lanes_ref(a.size);
     hipLaunchKernelGGL(atmo_precompute_reference_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- post-process
+// The tone map in the reference arithmetic (pt_present_set_arithmetic; device functions and specification: pt_postprocess_reference.hpp).
+// The contract kernel's shape (pt_helper_kernels.hip, pt_postprocess_kernel), for the same reasons: HBM-bound, 16 B read + 4 B written
+// per pixel, one whole float4 load and one whole uchar4 store per lane, no LDS; launched beside resident persistent wavefronts by the
+// present paths, so it raises its wave priority first.
+__global__ __launch_bounds__(256) void pt_postprocess_reference_kernel(const float4 *accum, uchar4 *out, size_t n)
+{
+    __builtin_amdgcn_s_setprio(3);
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (; i < n; i += stride) out[i] = ref::postprocess_pixel_ref(accum[i]);
+}
+
+hipError_t launch_postprocess_reference(const float4 *accum, void *outRgba8, size_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(pt_postprocess_reference_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, accum, (uchar4 *)outRgba8, n);
     return hipGetLastError();
 }
 

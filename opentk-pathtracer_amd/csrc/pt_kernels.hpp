@@ -240,6 +240,8 @@ struct AssembleArgs {
 hipError_t launch_assemble_bands(const AssembleArgs &a, hipStream_t stream);
 // ACES + gamma of PostProcessing/fragment.glsl: n RGBA32F pixels -> n RGBA8 pixels
 hipError_t launch_postprocess(const float4 *accum, void *outRgba8, size_t n, hipStream_t stream);
+// the same pass in the reference arithmetic (pt_integrate_reference.hip, pt_postprocess_reference.hpp)
+hipError_t launch_postprocess_reference(const float4 *accum, void *outRgba8, size_t n, hipStream_t stream);
 // linearise any environment into RGBA32F for read-back
 hipError_t launch_env_to_float(const void *env, int envSize, int envFormat, const float *srgbLut, float4 *out,
                                hipStream_t stream);

@@ -188,6 +188,7 @@ PT_DEV float linear_to_inverse_gamma(float v, float gamma)
     return f_fma(pt_exp(f_rcp(gamma) * pt_log(v)), 1.055f, -0.055f);
 }
 
+// (pt_postprocess_reference.hpp keeps a __host__ __device__ copy of this conversion, to_unorm8_ref: the two must stay the same function)
 PT_DEV unsigned char to_unorm8(float v) { return (unsigned char)(int)(f_clamp01(v) * 255.0f + 0.5f); }
 
 // compute.glsl:334-344 — PCG hash RNG; uint -> float conversion is round-to-nearest-even, /2^32 is exact.

@@ -18,7 +18,7 @@
 // With these choices the restatement equals the reference's own output bit for bit in ~98.6 % of the first-frame pixels of the
 // fixtures (the contract: 38.8 %).  Cost: several IEEE divisions per cuboid test (43 issue cycles each on gfx950) — see DESIGN.md.
 // The atmosphere precompute in this arithmetic: pt_atmosphere_reference.hpp (a switch of its own, pt_atmosphere_set_arithmetic).
-// Out of scope (stays in contract arithmetic): the post-process tone map.
+// The post-process tone map in this arithmetic: pt_postprocess_reference.hpp (a switch of its own, pt_present_set_arithmetic).
 //
 // The scalar primitives and vector helpers are __host__ __device__ so that a CPU test can compare them with the oracle bit for bit
 // (that test defines PT_REFERENCE_PRIMITIVES_ONLY: the integrator below needs the device-side scene and environment types).

@@ -52,6 +52,7 @@ struct PresentSlot {
     int fusedWord = 0;            // ... which host word of the feed ring its launch reports completed frames in,
     unsigned int fusedNeed = 0;   // ... and how many frames of that launch must be complete for the image to be
     bool fusedWaiting = false;    // ... and the frame that produces it (the one after the frame shown) has not been published yet: no event to wait for so far
+    int arithmetic = PT_ARITH_CONTRACT; // the present arithmetic the slot's image was issued under: a tone map that is re-done keeps it
 };
 } // namespace ptimpl
 
@@ -67,6 +68,7 @@ struct pt_renderer {
     int variant = 0;
     int arithmetic = PT_ARITH_CONTRACT; // pt_set_arithmetic: PT_ARITH_REFERENCE renders every frame with pt_integrate_reference_kernel
     int atmoArithmetic = PT_ARITH_CONTRACT; // pt_atmosphere_set_arithmetic: the kernel of the following pt_atmosphere_render calls
+    int presentArithmetic = PT_ARITH_CONTRACT; // pt_present_set_arithmetic: the tone-map kernel of the following presents (ptimpl::launch_tone_map)
 
     unsigned char basic[PT_BASIC_DATA_UBO_SIZE] = {0};   // host shadow of UBO 0 (travels as kernel argument)
     unsigned char atmoUbo[PT_ATMOSPHERE_UBO_SIZE] = {0}; // host shadow of UBO 2
@@ -289,6 +291,11 @@ int ensure_stripe(pt_handle h, int j); // create stripe stream j (j > 0) and its
 hipStream_t stripe_stream(pt_handle h, int j); // stripe 0 runs on the main stream
 // tone map this handle's rows into `dst` (RGBA8, compact rows) on h->stream, behind every frame rendered so far
 int tone_map_into(pt_handle h, void *dst);
+// the tone-map pass of a present in the given arithmetic (pt_present_set_arithmetic); every present path launches it through here
+inline hipError_t launch_tone_map(int arithmetic, const float4 *src, void *dstRgba8, size_t pixels, hipStream_t stream)
+{
+    return arithmetic == PT_ARITH_REFERENCE ? pt::launch_postprocess_reference(src, dstRgba8, pixels, stream) : pt::launch_postprocess(src, dstRgba8, pixels, stream);
+}
 // slot plumbing shared by the single and the group path
 int ensure_slot_device(pt_handle h, int slot, size_t pixels);
 int ensure_slot_host(pt_handle h, int slot, size_t pixels);

@@ -276,6 +276,12 @@ public:
     int Samples() const { int f = 0; Check(pt_get_frame_index(h_, &f), h_); return f * spp_; } // PathTracer.cs:112
     void Render() { Check(pt_render(h_, nullptr), h_); }                                        // PathTracer.cs:114-129
     void SetFrameBatch(int maxFrames) { Check(pt_set_frame_batch(h_, maxFrames), h_); }         // frames one launch may pipeline
+    // PT_ARITH_CONTRACT (default) or PT_ARITH_REFERENCE for the tone map of the presents that follow (no reference counterpart)
+    void SetPresentArithmetic(int mode)
+    {
+        if (mode != PT_ARITH_CONTRACT && mode != PT_ARITH_REFERENCE) throw std::invalid_argument("PathTracer::SetPresentArithmetic: bad mode");
+        Check(pt_present_set_arithmetic(h_, mode), h_);
+    }
     void SetSize(int width, int height) { Check(pt_set_size(h_, width, height), h_); width_ = width; height_ = height; } // :131-135
     void ResetRenderer() { Check(pt_reset(h_), h_); }                                           // :137-140
 

@@ -29,7 +29,7 @@ PT_MAX_IMAGE_DIM, PT_MAX_RAY_DEPTH, PT_MAX_SPP, PT_PRESENT_SLOTS = 32767, 4095, 
 PT_E_BAD_HANDLE, PT_E_BAD_ARGUMENT, PT_E_OUT_OF_RANGE, PT_E_NO_ENVIRONMENT, PT_E_HIP, PT_E_NO_DEVICE, PT_E_OOM = \
     -1, -2, -3, -4, -5, -6, -7
 PT_ENV_RGBA32F, PT_ENV_SRGB8_A8 = 0, 1
-PT_ARITH_CONTRACT, PT_ARITH_REFERENCE = 0, 1  # pt_set_arithmetic, pt_atmosphere_set_arithmetic
+PT_ARITH_CONTRACT, PT_ARITH_REFERENCE = 0, 1  # pt_set_arithmetic, pt_atmosphere_set_arithmetic, pt_present_set_arithmetic
 
 
 class NativeError(RuntimeError):
@@ -209,6 +209,7 @@ def load() -> C.CDLL:
         "pt_present_rgba8_async": [vp, C.c_int],
         "pt_present_wait": [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), ip],
         "pt_present_bind_device_image": [vp, C.c_int, vp, C.c_size_t],
+        "pt_present_set_arithmetic": [vp, C.c_int],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

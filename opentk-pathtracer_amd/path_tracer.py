@@ -261,6 +261,14 @@ class PathTracer:
         it in ~98.6 % of pixels, slower).  Frames rendered before keep their arithmetic; the accumulation is not reset."""
         check(self._lib.pt_set_arithmetic(self._h, mode), self._h)
 
+    def SetPresentArithmetic(self, mode: int) -> None:
+        """Arithmetic of the tone map of the presents that follow (Present, PostProcessDevice, PresentAsync; pt_present_set_arithmetic):
+        native.PT_ARITH_CONTRACT (default) or native.PT_ARITH_REFERENCE (the GL reference's own arithmetic: its float colour bit for bit on
+        the reference's fixture).  Independent of SetArithmetic and AtmosphericScatterer.SetArithmetic; the image is not touched."""
+        if mode not in (native.PT_ARITH_CONTRACT, native.PT_ARITH_REFERENCE):
+            raise ValueError("mode must be native.PT_ARITH_CONTRACT or native.PT_ARITH_REFERENCE")
+        check(self._lib.pt_present_set_arithmetic(self._h, mode), self._h)
+
     def SetFrameBatch(self, max_frames: int) -> None:
         """Largest number of consecutive Render() calls one launch pipelines (1 = launch every frame at once)."""
         check(self._lib.pt_set_frame_batch(self._h, max_frames), self._h)
