@@ -18,12 +18,32 @@ LIB_EXACT_PATH = os.path.join(HERE, "_build", "libpt_oracle_exact.so")  # fideli
 LIB_NANMARK_PATH = os.path.join(HERE, "_build", "libpt_oracle_nanmark.so")  # diagnostic: env lookups with a NaN direction return 1000
 LIB_MARGINS_PATH = os.path.join(HERE, "_build", "libpt_oracle_margins.so")  # decision margins per pixel (tests/test_decision_margins.py)
 LIB_PERTURB_PATH = os.path.join(HERE, "_build", "libpt_oracle_perturb.so")  # witness build: one primitive a chosen number of ulps off
+# what the libraries are built from (oracle/Makefile): the contract, its hooks, and the study units that #include it
+SOURCES = ("pt_oracle.c", "pt_oracle_hooks.h", "pt_oracle_llvmpipe.h", os.path.join("study", "pt_oracle_witness.c"),
+           os.path.join("study", "pt_oracle_margins.c"), "Makefile")
+
+# Oracle(perturb=True).set_base_variant(bits): the conforming implementation the witness library computes (0 = the contract).
+NEVER_FUSED = 1            # a * b + c outside the primitives with two roundings
+EXACT_DIV_SQRT = 2         # correctly rounded 1 / x, 1 / sqrt(x), sqrt(x)
+LITERAL_DIVISION = 4       # the literal a / b where the contract multiplies by a reciprocal (cuboid slabs, sphere normal, throughput, ndc)
+MATVEC_W_FIRST = 1 << 3    # bits 8 + 16, the order of a matrix-vector product's column terms: 0 = the contract's x, y, z, w chain; 1 = w, z, y, x;
+MATVEC_LLVMPIPE = 2 << 3   # 2 = ((w + x) + z) + y, llvmpipe's;
+MATVEC_XYWZ = 3 << 3       # 3 = x, y, w, z
+DOT_X_PLUS_YZ = 1 << 5     # bits 32 + 64, the order of a dot product's terms: 0 = the contract's x, y, z chain; 1 = y, z, x (llvmpipe's);
+DOT_ZXY = 2 << 5           # 2 = z, x, y
+LLVM_MATH = 1 << 7         # sin, cos, exp, pow as llvmpipe's gallivm evaluates them (oracle/pt_oracle_llvmpipe.h; bit-identical on the probe)
+MIX_AS_LERP = 1 << 8       # mix(x, y, a) = x + a (y - x)
+SAMPLER_LERPS = 1 << 9     # the cube filter as two nested fused lerps
+# every one of llvmpipe's choices the oracle restates (= 951): THE ORACLE OF THE SHIPPED REFERENCE-ARITHMETIC MODES (pt_set_arithmetic,
+# pt_atmosphere_set_arithmetic, pt_present_set_arithmetic are checked on the GPU against the witness library at this base variant)
+LLVMPIPE = NEVER_FUSED | EXACT_DIV_SQRT | LITERAL_DIVISION | MATVEC_LLVMPIPE | DOT_X_PLUS_YZ | LLVM_MATH | MIX_AS_LERP | SAMPLER_LERPS
+assert LLVMPIPE == 951
 
 
 def build(force: bool = False) -> None:
-    src = os.path.join(HERE, "pt_oracle.c")
+    newest = max(os.path.getmtime(os.path.join(HERE, s)) for s in SOURCES)
     libs = (LIB_PATH, LIB_TRUEDIV_PATH, LIB_EXACT_PATH, LIB_NANMARK_PATH, LIB_MARGINS_PATH, LIB_PERTURB_PATH)
-    stale = not all(os.path.exists(p) for p in libs) or min(os.path.getmtime(p) for p in libs) < os.path.getmtime(src)
+    stale = not all(os.path.exists(p) for p in libs) or min(os.path.getmtime(p) for p in libs) < newest
     if force or stale:
         subprocess.run(["make", "-C", HERE, "-B" if force else "-s", "all"], check=True, capture_output=True)
 
@@ -110,13 +130,14 @@ class Oracle:
 
     def set_base_variant(self, bits: int) -> None:
         """Oracle(perturb=True) only: the conforming implementation the witness searches and replays run around — 1 never fused, 2 correctly
-        rounded 1/x, sqrt, 1/sqrt, 4 literal divisions; 7 = llvmpipe's choices, 0 = the contract."""
+        rounded 1/x, sqrt, 1/sqrt, 4 literal divisions, ... (the named bits at the top of this module); LLVMPIPE = all of llvmpipe's choices,
+        0 = the contract."""
         assert self.lib.pto_set_base_variant(int(bits)) == 0, "this oracle build has no witness hooks (Oracle(perturb=True))"
 
     def set_ensemble(self, seed: int, amplitude: int = 16) -> None:
         """Oracle(perturb=True) only: the library becomes ensemble member `seed` (0: off) — ONE conforming implementation that differs from the
         contract everywhere at once: every primitive call up to min(amplitude, its allowance) ulps off, every multiply-add fused or not, every
-        division literal or by reciprocal, each a fixed function of the member and the operands (pt_oracle.c, ens_hash)."""
+        division literal or by reciprocal, each a fixed function of the member and the operands (study/pt_oracle_witness.c, ens_hash)."""
         if not hasattr(self.lib.pto_set_ensemble, "_typed"):
             self.lib.pto_set_ensemble.restype = C.c_int
             self.lib.pto_set_ensemble.argtypes = [C.c_uint, C.c_int]
@@ -218,8 +239,8 @@ class Oracle:
                             focal_length=20.0, aperture=0.14, num_frames=1, threads=None, dump_each=False):
         """Oracle(margins=True) only: frames [0, num_frames) accumulated from zero -> (image (H, W, 4), margin (H, W), cont (H, W)):
         per pixel the smallest relative error eps of the arithmetic's primitives that flips one of the data-dependent comparisons of
-        any frame so far, and the largest flip-free absolute colour error per unit eps of any frame so far (pt_oracle.c,
-        PT_ORACLE_MARGINS); with dump_each all three per frame."""
+        any frame so far, and the largest flip-free absolute colour error per unit eps of any frame so far
+        (study/pt_oracle_margins.c); with dump_each all three per frame."""
         basic, objs, env = self._inputs(basic_ubo, objects_ubo, env_faces)
         p = self._params(width, height, num_spheres, num_cuboids, ray_depth, spp, focal_length, aperture, env)
         threads = threads or os.cpu_count() or 1

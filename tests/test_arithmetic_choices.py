@@ -31,6 +31,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import __graft_entry__ as graft
 import fixtures
 import tolerances as tol
 
@@ -39,8 +40,11 @@ _spec = importlib.util.spec_from_file_location("glsl_run", os.path.join(ROOT, "o
 ref = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(ref)
 
-NEVER_FUSED, EXACT_DIV_SQRT, LITERAL_DIVISION, MATVEC_W_FIRST, MATVEC_LLVMPIPE, DOT_X_PLUS_YZ, LLVM_MATH, MIX_AS_LERP, SAMPLER_LERPS = 1, 2, 4, 1 << 3, 2 << 3, 1 << 5, 1 << 7, 1 << 8, 1 << 9
-LLVMPIPE = NEVER_FUSED | EXACT_DIV_SQRT | LITERAL_DIVISION | MATVEC_LLVMPIPE | DOT_X_PLUS_YZ | LLVM_MATH | MIX_AS_LERP | SAMPLER_LERPS   # (LLVM_MATH: its sin, cos, exp, pow — exact, see the probe below)
+# the bits of pto_set_base_variant, named where the binding documents them (oracle/pt_oracle.py); LLVMPIPE = all of llvmpipe's choices, 951
+# (LLVM_MATH: its sin, cos, exp, pow — exact, see the probe below)
+_po = graft.load_oracle()
+NEVER_FUSED, EXACT_DIV_SQRT, LITERAL_DIVISION, MATVEC_W_FIRST, MATVEC_LLVMPIPE = _po.NEVER_FUSED, _po.EXACT_DIV_SQRT, _po.LITERAL_DIVISION, _po.MATVEC_W_FIRST, _po.MATVEC_LLVMPIPE
+DOT_X_PLUS_YZ, LLVM_MATH, MIX_AS_LERP, SAMPLER_LERPS, LLVMPIPE = _po.DOT_X_PLUS_YZ, _po.LLVM_MATH, _po.MIX_AS_LERP, _po.SAMPLER_LERPS, _po.LLVMPIPE
 
 
 @pytest.fixture(scope="module")
@@ -103,7 +107,7 @@ def test_the_atmosphere_cubes_band_is_the_same_named_choices(variants, name):
 
 
 # ---- llvmpipe's built-ins, probed live (build container only).  The witness build restates sin, cos, exp, pow, exp2, log2 as Mesa's gallivm
-# evaluates them (oracle/pt_oracle.c "base variant bit 128"; Mesa is a dependency of the reference's test rig, absent from /root/reference:
+# evaluates them (oracle/pt_oracle_llvmpipe.h, base variant bit 128; Mesa is a dependency of the reference's test rig, absent from /root/reference:
 # restated from its published algorithm) — and the probe below shows the restatement is EXACT: bit-identical with the live llvmpipe on
 # 65,536 arguments per function.  It also measures what the contract's allowances rest on: llvmpipe's a / b, 1 / x and sqrt are correctly
 # rounded, inversesqrt(x) is 1 / sqrt(x) with two roundings, a * b + c in shader code is never fused (its built-ins' own polynomials are).

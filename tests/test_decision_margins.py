@@ -1,7 +1,7 @@
 """Layer-2 parity as a PER-PIXEL statement (round 5).
 
 Layer 2 (oracle ~ reference) used to be a percentage: "x % of the pixels lie inside 1e-4 * max(1, |ref|), the rest are assumed to be
-branch flips" (tests/tolerances.py, thresholds.json).  The oracle's -DPT_ORACLE_MARGINS build (oracle/pt_oracle.c, "decision margins")
+branch flips" (tests/tolerances.py, thresholds.json).  The oracle's margins build (oracle/study/pt_oracle_margins.c, "decision margins")
 makes the assumption checkable: next to every path it carries a first-order bound of the path's own error per unit of relative error eps
 of the arithmetic's primitives, and records per pixel
     margin = the smallest eps at which one of the pixel's data-dependent comparisons (compute.glsl:169,201,208,234,247,269,293,347-350,
@@ -21,8 +21,11 @@ HIP path's too; `-m gpu`: test_gpu_decision_margins below makes it on the GPU's 
 import numpy as np
 import pytest
 
+import __graft_entry__ as graft
 import fixtures
 import tolerances as tol
+
+LLVMPIPE = graft.load_oracle().LLVMPIPE  # (951) every one of llvmpipe's choices the oracle restates: oracle/pt_oracle.py
 
 TAU = 2e-8           # relative error of the arithmetic's primitives (1 ulp of binary32 = 6e-8)
 _REPORT = []
@@ -75,7 +78,7 @@ def test_every_out_of_band_pixel_of_the_full_size_configs_sits_on_a_knife_edge(o
 
 # ---- constructive witnesses (round 6).  "Sits on a knife edge" is an upper bound from a first-order analysis; the converse is SHOWN per
 # pixel: a pixel of the reference that the contract misses is HIT — inside the band — by a neighbouring conforming implementation of the
-# same GLSL, found by oracle/pt_oracle.c pto_witness_search (witness build, -DPT_ORACLE_PERTURB) and replayed here through
+# same GLSL, found by pto_witness_search (witness build, oracle/study/pt_oracle_witness.c) and replayed here through
 # pto_render_pixel_variant:
 #   1  ONE data-dependent comparison of the pixel's path inverted (operands closer than 1e-6 of their scale — ~17 ulps; until the ensemble test showed two
 #      spurious ones the search allowed 1e-2, and tightening it 10,000-fold lost no witness: 378 / 36 / 43 / 3 of 460 either way), everything else the contract;
@@ -94,7 +97,7 @@ def test_every_out_of_band_pixel_of_the_full_size_configs_sits_on_a_knife_edge(o
 # environment), none is merely moved out of the band by a single call one ulp off (demonstrably unstable) without a neighbour landing inside
 # — their neighbours scatter over tens to thousands of bands and the search enumerates six sites at a time —, 0.4 % neither (until the search also ran around llvmpipe's SUMMATION ORDERS: 82 / 7 / 9 / 1.3 %).  Gated: the share reached, and that no pixel is without
 # any of the three.  The global variants of the earlier rounds (one primitive off EVERYWHERE: 40-60 %) are subsumed.
-BASES = (0, 951, 7)    # the implementations the search runs around: the contract, then llvmpipe's own choices — 951: never fused, correctly rounded
+BASES = (0, LLVMPIPE, 7)    # the implementations the search runs around: the contract, then llvmpipe's own choices — LLVMPIPE (951): never fused, correctly rounded
                        # 1/x, sqrt, 1/sqrt, literal divisions, its summation orders, its own sin / cos / exp / pow, mix and the cube filter as lerps
                        # (tests/test_arithmetic_choices.py: with these the restatement renders 94 % of the reference's pixels bit for bit); 7: the
                        # first three only — as conforming as the contract, and much nearer to the reference where paths amplify.  Share reached:

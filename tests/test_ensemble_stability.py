@@ -2,7 +2,7 @@
 
 tests/test_decision_margins.py bounds a pixel's sensitivity from one side with a first-order error analysis; because the bound pays every
 bounce's worst-case amplification it certifies only 13 - 55 % of the pixels.  This test measures the sensitivity instead.  The oracle's
-witness build (oracle/pt_oracle.c, -DPT_ORACLE_PERTURB, pto_set_ensemble) turns into ensemble MEMBERS: each member is ONE conforming
+witness build (oracle/study/pt_oracle_witness.c, pto_set_ensemble) turns into ensemble MEMBERS: each member is ONE conforming
 implementation of the reference's GLSL that differs from the pt-f32 contract everywhere at once, the way a real driver does —
 
   * every call of 1/x, inversesqrt, sqrt, sin, cos, exp, pow(x, 5) returns a result up to its allowance of ulps off (2, 2, 2, 4, 4, 4, 16:
@@ -44,7 +44,7 @@ import tolerances as tol
 
 MEMBERS = tuple(0x1234567 * k + k for k in range(1, 9))   # eight conforming neighbours of the contract (2 / 4 / 8 / 16 members: 37 / 2 / 0 / 0
                                                           # certified pixels outside the band, 98.8 / 98.5 / 98.3 / 98.2 % certified)
-AMPLITUDE = 16      # ulps, capped per primitive by its allowance (pt_oracle.c ens_allow)
+AMPLITUDE = 16      # ulps, capped per primitive by its allowance (oracle/study/pt_oracle_witness.c ens_allow)
 THETA = 0.5         # a member may move a certified pixel by at most half the band
 MIN_SHARE = 0.95    # measured 95.3 % (256 spheres) ... 99.9 %
 _REPORT = []

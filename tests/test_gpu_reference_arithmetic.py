@@ -7,13 +7,14 @@ import math
 import numpy as np
 import pytest
 
+import __graft_entry__ as graft
 import configs
 import fixtures
 import tolerances as tol
 
 pytestmark = pytest.mark.gpu
 
-LLVMPIPE = 951  # tests/test_arithmetic_choices.py LLVMPIPE: every one of llvmpipe's choices the oracle restates
+LLVMPIPE = graft.load_oracle().LLVMPIPE  # (951) every one of llvmpipe's choices the oracle restates: oracle/pt_oracle.py
 
 
 def bits(a):

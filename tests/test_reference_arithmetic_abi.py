@@ -1,6 +1,6 @@
 """pt_set_arithmetic without a GPU: the ABI of the reference-arithmetic mode (header, exports, argument checks, Python binding) and the
 scalar primitives of csrc/pt_math_reference.hpp, host-compiled and compared bit for bit with the oracle's restatement of llvmpipe's
-built-ins (oracle/pt_oracle.c, witness build: pto_llvmpipe_like) and with numpy's correctly rounded 1 / x, sqrt and 1 / sqrt."""
+built-ins (oracle/pt_oracle_llvmpipe.h, witness build: pto_llvmpipe_like) and with numpy's correctly rounded 1 / x, sqrt and 1 / sqrt."""
 import ctypes as C
 import os
 import re

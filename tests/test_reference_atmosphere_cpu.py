@@ -14,12 +14,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import __graft_entry__ as graft
 import fixtures
 import tolerances as tol
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mi355pt.h")
-LLVMPIPE = 951  # tests/test_arithmetic_choices.py LLVMPIPE: every one of llvmpipe's choices the oracle restates
+LLVMPIPE = graft.load_oracle().LLVMPIPE  # (951) every one of llvmpipe's choices the oracle restates: oracle/pt_oracle.py
 
 
 # ------------------------------------------------------------------------------------------------ (1) ABI
