@@ -293,6 +293,42 @@ PT_API int pt_atmosphere_set_arithmetic(pt_handle h, int mode);
  * map).  Any other mode: PT_E_BAD_ARGUMENT, and the previous mode stays in force. */
 PT_API int pt_present_set_arithmetic(pt_handle h, int mode);
 
+/* ---- first-hit query: "what is under this pixel?" ------------------------------------------------------------- */
+
+/* The reference answers this on the CPU, with a second ray caster: src/Render/Gui.cs:223-233 -> MainWindow.RayTrace,
+ * src/MainWindow.cs:302-318 (Sphere.IntersectsRay / Cuboid.IntersectsRay on a pinhole ray through the cursor: other formulas, no lens,
+ * no sub-pixel offset, not the shader's entry-distance acceptance rule, compute.glsl:234,247 — so a click can select another object
+ * than the one the rendered pixel shows, most often inside or near glass).  These calls replace it with the integrator's own ray:
+ * for pixel (x, y) the record describes the first intersection of the ray of SAMPLE 0 OF FRAME frame_index, exactly as pt_render
+ * traces it for that pixel and frame — seed from (x, y, frame), the two sub-pixel draws, GetWorldSpaceRay, the two lens draws with
+ * the handle's current focal length and aperture, RayTrace over spheres 0..Ns-1 then cuboids 0..Nc-1 with the reference's
+ * acceptance rule and visiting order — in the CONTRACT arithmetic, whatever the three arithmetic switches say.
+ * Record = 32 bytes = 8 words, rows like the image (row 0 = bottom, global pixel coordinates under tiling):
+ *   words 0-2 ray origin; word 3 t = the T RayTrace leaves (the smallest positive root: the EXIT distance when the origin lies inside
+ *   the winner), +inf on a miss; words 4-6 ray direction; word 7 id as int32 bits: -1 miss, i = sphere i, PT_MAX_SPHERES + j = cuboid j.
+ * Read: the current camera blob, scene blob and parameters.  Neither read nor written: the accumulation image, the frame counter, the
+ * environment (none is needed), the three arithmetic switches. */
+
+/* Gui.cs:223-233 / MainWindow.cs:302-318 for EVERY pixel of this handle's rows (an id / depth image for an outline or denoising
+ * pass): stream-ordered and asynchronous; launches what is pending first.  The rows x width x 32-byte device buffer is allocated by
+ * the first call after pt_set_size / pt_set_tile / pt_set_interleaved_tile, which free it (never by pt_render).
+ * frame_index < 0: PT_E_BAD_ARGUMENT.  Group handles: every device renders its rows. */
+PT_API int pt_first_hit_render(pt_handle h, int frame_index);
+/* The records of the last pt_first_hit_render (Gui.cs:223-233 / MainWindow.cs:302-318 read their answer on the host as well): blocks,
+ * copies this handle's rows into dst; row_pitch_bytes >= width*32, 0 = tightly packed.  Group handles gather the rows of all devices.
+ * PT_E_BAD_ARGUMENT when nothing was rendered since the last pt_set_size / pt_set_tile / pt_set_interleaved_tile. */
+PT_API int pt_first_hit_read(pt_handle h, void *dst, size_t row_pitch_bytes);
+/* Device pointer + byte size of those records (stream-ordered behind the pt_first_hit_render that wrote them; valid until the next
+ * resize / re-tiling), for a device-side consumer of the id / depth image — no counterpart in Gui.cs:223-233 / MainWindow.cs:302-318,
+ * whose answer lives on the host.  Single-GPU handles only, like pt_postprocess_device. */
+PT_API int pt_first_hit_device_ptr(pt_handle h, void **out, size_t *bytes);
+/* MainWindow.RayTrace for one pixel — the call Gui.cs:223-233 makes on a click (MainWindow.cs:302-318): blocks; one 8x8-tile launch and
+ * a 32-byte copy; the records of pt_first_hit_render are not touched.  *out_id as word 7 above; out_t, out_origin, out_dir may be
+ * NULL (out_t: e.g. the FocalLength that focuses the lens on the object).  x / y outside the image, or — on a tiled handle — a row
+ * the handle does not own: PT_E_OUT_OF_RANGE; out_id == NULL or frame_index < 0: PT_E_BAD_ARGUMENT.  Group handles: the device that
+ * owns the row answers. */
+PT_API int pt_pick(pt_handle h, int x, int y, int frame_index, int *out_id, float *out_t, float out_origin[3], float out_dir[3]);
+
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);
 PT_API int pt_device_count(void);

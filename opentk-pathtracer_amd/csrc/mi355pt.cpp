@@ -286,6 +286,15 @@ int ensure_stripe(pt_handle h, int j)
 }
 
 hipStream_t stripe_stream(pt_handle h, int j) { return j == 0 ? h->stream : h->stripeStream[j]; }
+
+int free_first_hit(pt_handle h)
+{
+    if (!h->dFirstHit) return PT_OK;
+    PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_first_hit_render may still write it)
+    PT_HIP(h, hipFree(h->dFirstHit));
+    h->dFirstHit = nullptr;
+    return PT_OK;
+}
 } // namespace ptimpl
 
 namespace {
@@ -534,6 +543,8 @@ PT_API int pt_destroy(pt_handle h)
     if (h->dEnv) (void)hipFree(h->dEnv);
     if (h->dAccum) (void)hipFree(h->dAccum);
     if (h->dRgba8) (void)hipFree(h->dRgba8);
+    if (h->dFirstHit) (void)hipFree(h->dFirstHit);
+    if (h->dPick) (void)hipFree(h->dPick);
     if (h->dTimeline) (void)hipFree(h->dTimeline);
     if (h->evBegin) (void)hipEventDestroy(h->evBegin);
     if (h->evEnd) (void)hipEventDestroy(h->evEnd);
@@ -553,6 +564,7 @@ PT_API int pt_set_size(pt_handle h, int width, int height)
     if (int rc = flush_frames(h)) return rc; // pending frames were rendered with the inputs as they were
     if (int rc = bind_device(h)) return rc;
     if (int rc = join_stripes(h)) return rc; // (the launches so far — and their hand-over repair passes — belong to the buffers as they are)
+    if (int rc = ptimpl::free_first_hit(h)) return rc;
     h->width = width;
     h->height = height;
     h->y0 = 0;
@@ -573,6 +585,7 @@ PT_API int pt_set_tile(pt_handle h, int y0, int rows)
     if (y0 < 0 || rows <= 0 || y0 + rows > h->height) return fail(h, PT_E_BAD_ARGUMENT, "tile outside the image");
     if (int rc = bind_device(h)) return rc;
     if (int rc = join_stripes(h)) return rc; // (see pt_set_size)
+    if (int rc = ptimpl::free_first_hit(h)) return rc;
     h->y0 = y0;
     h->rows = rows;
     h->bandRows = 0;
@@ -599,6 +612,7 @@ PT_API int pt_set_interleaved_tile(pt_handle h, int rank, int world, int band_ro
     }
     if (rows <= 0) return fail(h, PT_E_BAD_ARGUMENT, "this rank owns no rows (image too small for world * band_rows)");
     if (int rc = join_stripes(h)) return rc; // (see pt_set_size)
+    if (int rc = ptimpl::free_first_hit(h)) return rc;
     h->y0 = 0;
     h->rows = (int)rows;
     h->bandRows = band_rows;
@@ -2073,6 +2087,111 @@ PT_API int pt_timer_end(pt_handle h, float *out_ms)
     PT_HIP(h, hipEventRecord(h->evEnd, h->stream));
     PT_HIP(h, hipEventSynchronize(h->evEnd));
     PT_HIP(h, hipEventElapsedTime(out_ms, h->evBegin, h->evEnd));
+    return PT_OK;
+}
+
+// ---- first-hit query (pt_first_hit.hip): what src/Render/Gui.cs:223-233 -> src/MainWindow.cs:302-318 answer on the CPU, for the ray the
+// integrator traces.  Reads the camera shadow, the scene blob and the parameters; touches neither the accumulation image, the frame
+// counter, the cached tile masks, the environment nor an arithmetic switch.
+static_assert(pt::kFirstHitCuboidBase == PT_MAX_SPHERES, "first-hit ids: cuboid j is PT_MAX_SPHERES + j");
+
+// the kernel argument of a first-hit launch over this handle's rows (only the fields stage_scene, primary_ray and global_row read)
+static void first_hit_args(pt_handle h, pt::FrameArgs &a, int frame_index)
+{
+    std::memset(&a, 0, sizeof a);
+    std::memcpy(a.invProj, h->basic, 64);
+    std::memcpy(a.invView, h->basic + 64, 64);
+    std::memcpy(a.viewPos, h->basic + 128, 12);
+    a.focalLength = h->focalLength;
+    a.apertureDiameter = h->apertureDiameter;
+    a.width = h->width;
+    a.height = h->height;
+    a.invW = 1.0f / (float)h->width; // (as fill_frame_args)
+    a.invH = 1.0f / (float)h->height;
+    a.y0 = h->y0;
+    a.rows = h->rows;
+    a.bandRows = h->bandRows;
+    a.bandWorld = h->bandWorld;
+    a.bandRank = h->bandRank;
+    a.numSpheres = h->numSpheres;
+    a.numCuboids = h->numCuboids;
+    a.rayDepth = 1;
+    a.spp = 1;
+    a.batchFrames = 1;
+    a.frame = frame_index;
+    a.objects = h->dObjects;
+    a.tilesX = (h->width + 7) / 8;
+    a.tilesY = (h->rows + 7) / 8;
+}
+
+PT_API int pt_first_hit_render(pt_handle h, int frame_index)
+{
+    PT_CHECK_HANDLE(h);
+    if (frame_index < 0) return fail(h, PT_E_BAD_ARGUMENT, "frame_index must be >= 0");
+    PT_FAN_OUT(h, pt_first_hit_render(part, frame_index));
+    if (int rc = bind_device(h)) return rc;
+    if (int rc = join_stripes(h)) return rc; // (pending frames are launched, an open frame-fed launch is closed: like every non-render entry point)
+    if (!h->dFirstHit) PT_HIP(h, hipMalloc((void **)&h->dFirstHit, h->tilePixels() * 2 * sizeof(float4)));
+    pt::FrameArgs a;
+    first_hit_args(h, a, frame_index);
+    PT_HIP(h, pt::launch_first_hit(a, h->dFirstHit, -1, h->stream));
+    return PT_OK;
+}
+
+PT_API int pt_first_hit_read(pt_handle h, void *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (!dst) return fail(h, PT_E_BAD_ARGUMENT, "dst == NULL");
+    const size_t rowBytes = (size_t)h->width * 32;
+    if (row_pitch_bytes == 0) row_pitch_bytes = rowBytes;
+    if (row_pitch_bytes < rowBytes) return fail(h, PT_E_BAD_ARGUMENT, "row pitch smaller than a row");
+    if (h->isGroup()) return ptimpl::group_first_hit_read(h, dst, row_pitch_bytes);
+    if (!h->dFirstHit) return fail(h, PT_E_BAD_ARGUMENT, "no pt_first_hit_render since the last pt_set_size / pt_set_tile / pt_set_interleaved_tile");
+    if (int rc = bind_device(h)) return rc;
+    PT_HIP(h, hipMemcpy2DAsync(dst, row_pitch_bytes, h->dFirstHit, rowBytes, rowBytes, (size_t)h->rows, hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(h, hipStreamSynchronize(h->stream));
+    return PT_OK;
+}
+
+PT_API int pt_first_hit_device_ptr(pt_handle h, void **out, size_t *bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (h->isGroup()) return fail(h, PT_E_BAD_ARGUMENT, "pt_first_hit_device_ptr is not available on a group handle");
+    if (!h->dFirstHit) return fail(h, PT_E_BAD_ARGUMENT, "no pt_first_hit_render since the last pt_set_size / pt_set_tile / pt_set_interleaved_tile");
+    if (out) *out = h->dFirstHit;
+    if (bytes) *bytes = h->tilePixels() * 2 * sizeof(float4);
+    return PT_OK;
+}
+
+PT_API int pt_pick(pt_handle h, int x, int y, int frame_index, int *out_id, float *out_t, float out_origin[3], float out_dir[3])
+{
+    PT_CHECK_HANDLE(h);
+    if (!out_id) return fail(h, PT_E_BAD_ARGUMENT, "out_id == NULL");
+    if (frame_index < 0) return fail(h, PT_E_BAD_ARGUMENT, "frame_index must be >= 0");
+    if (x < 0 || x >= h->width || y < 0 || y >= h->height) return fail(h, PT_E_OUT_OF_RANGE, "pixel outside the image");
+    if (h->isGroup()) return ptimpl::group_pick(h, x, y, frame_index, out_id, out_t, out_origin, out_dir);
+    // image row -> row inside this handle's storage (the inverse of the kernels' global_row)
+    int ly;
+    if (h->bandRows == 0) {
+        ly = y - h->y0;
+    } else {
+        const int band = y / h->bandRows;
+        ly = band % h->bandWorld == h->bandRank ? (band / h->bandWorld) * h->bandRows + y % h->bandRows : -1;
+    }
+    if (ly < 0 || ly >= h->rows) return fail(h, PT_E_OUT_OF_RANGE, "this handle does not own the pixel's row (pt_set_tile / pt_set_interleaved_tile)");
+    if (int rc = bind_device(h)) return rc;
+    if (int rc = join_stripes(h)) return rc;
+    if (!h->dPick) PT_HIP(h, hipMalloc((void **)&h->dPick, 64 * 2 * sizeof(float4)));
+    pt::FrameArgs a;
+    first_hit_args(h, a, frame_index);
+    PT_HIP(h, pt::launch_first_hit(a, h->dPick, (ly >> 3) * a.tilesX + (x >> 3), h->stream));
+    float rec[8];
+    PT_HIP(h, hipMemcpyAsync(rec, h->dPick + 2 * ((ly & 7) * 8 + (x & 7)), sizeof rec, hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(out_id, &rec[7], sizeof(int));
+    if (out_t) *out_t = rec[3];
+    if (out_origin) std::memcpy(out_origin, &rec[0], 12);
+    if (out_dir) std::memcpy(out_dir, &rec[4], 12);
     return PT_OK;
 }
 

@@ -84,12 +84,13 @@ int ensure_buffer(pt_handle g, void **buf, size_t *cap, size_t need, hipStream_t
 // Pull the parts' rows (src[i] = compact rows of part i on its device, bpp bytes per pixel; part i's rows may be read
 // once ready[i] has fired) into the assembled width x height image `full` on the root device, all on root-device
 // stream `st`.  `stage` / `stageCap` = the staging buffer to use for block-cyclic ownership.
+// `units`: elements of bpp bytes per pixel (1 for the images; 2 for the 32-byte first-hit records, moved as two 16-byte elements).
 int gather_on_root(pt_handle g, const std::vector<const void *> &src, const std::vector<hipEvent_t> &ready, int bpp,
-                   void *full, void **stage, size_t *stageCap, hipStream_t st)
+                   void *full, void **stage, size_t *stageCap, hipStream_t st, int units = 1)
 {
     const int G = (int)g->parts.size();
     if (int rc = root_device(g)) return rc;
-    const size_t rowBytes = (size_t)g->width * bpp;
+    const size_t rowBytes = (size_t)g->width * units * bpp;
     const bool bands = banded(g);
     if (bands)
         if (int rc = ensure_buffer(g, stage, stageCap, (size_t)g->height * rowBytes, st)) return rc;
@@ -101,12 +102,12 @@ int gather_on_root(pt_handle g, const std::vector<const void *> &src, const std:
         char *dst = bands ? (char *)*stage + off * bpp : (char *)full + (size_t)p->y0 * rowBytes;
         PT_HIP(g, hipMemcpyPeerAsync(dst, g->device, src[i], p->device, (size_t)p->rows * rowBytes, st));
         aa.partOffset[i] = off;
-        off += (size_t)p->rows * g->width;
+        off += (size_t)p->rows * g->width * units;
     }
     if (bands) {
         aa.stage = *stage;
         aa.out = full;
-        aa.width = g->width;
+        aa.width = g->width * units;
         aa.height = g->height;
         aa.bandRows = g->parts[0]->bandRows;
         aa.world = G;
@@ -284,6 +285,39 @@ int group_present_async(pt_handle g, int slot)
     gs.rows = g->height;
     gs.width = g->width;
     return PT_OK;
+}
+
+// pt_first_hit_read on a group: the parts' record rows gathered like the accumulation image (each record = two 16-byte elements)
+int group_first_hit_read(pt_handle g, void *dst, size_t row_pitch_bytes)
+{
+    std::vector<const void *> src;
+    std::vector<hipEvent_t> ready;
+    for (pt_handle p : g->parts) {
+        if (!p->dFirstHit) return fail(g, PT_E_BAD_ARGUMENT, "no pt_first_hit_render since the last pt_set_size / pt_multi_set_partition");
+        if (int rc = ptimpl::bind_device(p)) return part_fail(g, p, rc);
+        PT_HIP(g, hipEventRecord(p->gatherReady, p->stream));
+        src.push_back(p->dFirstHit);
+        ready.push_back(p->gatherReady);
+    }
+    if (int rc = root_device(g)) return rc;
+    const size_t rowBytes = (size_t)g->width * 32;
+    if (int rc = ensure_buffer(g, &g->dGatherFull, &g->gatherFullBytes, (size_t)g->height * rowBytes, g->stream)) return rc;
+    if (int rc = gather_on_root(g, src, ready, 16, g->dGatherFull, &g->dGatherStage, &g->gatherStageBytes, g->stream, 2)) return rc;
+    PT_HIP(g, hipMemcpy2DAsync(dst, row_pitch_bytes, g->dGatherFull, rowBytes, rowBytes, (size_t)g->height, hipMemcpyDeviceToHost, g->stream));
+    PT_HIP(g, hipStreamSynchronize(g->stream));
+    return PT_OK;
+}
+
+// pt_pick on a group: the part that owns the pixel's row answers
+int group_pick(pt_handle g, int x, int y, int frame_index, int *out_id, float *out_t, float *out_origin, float *out_dir)
+{
+    for (pt_handle p : g->parts) {
+        const bool owns = p->bandRows == 0 ? (y >= p->y0 && y < p->y0 + p->rows) : ((y / p->bandRows) % p->bandWorld == p->bandRank);
+        if (!owns) continue;
+        int rc = pt_pick(p, x, y, frame_index, out_id, out_t, out_origin, out_dir);
+        return rc == PT_OK ? rc : part_fail(g, p, rc);
+    }
+    return fail(g, PT_E_OUT_OF_RANGE, "no device of the group owns the pixel's row");
 }
 
 int group_timer_end(pt_handle g, float *out_ms)

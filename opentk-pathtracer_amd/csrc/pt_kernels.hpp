@@ -220,6 +220,11 @@ hipError_t launch_integrate_reference(const FrameArgs &a, hipStream_t stream);
 // ... followed by ONE of these: abandon word and ticket counters back to what a fresh chain expects
 hipError_t launch_repair_done(unsigned int *abandonWord, unsigned int *queueMain, unsigned int expectMain, unsigned int *queueChain,
                               unsigned int expectChain, unsigned int *ctl, hipStream_t stream);
+// the first-hit query (pt_first_hit.hip; contract arithmetic): per pixel of the launch (a.tilesX / a.tilesY set, a.frame = the frame whose
+// sample 0 is traced) two float4 — (origin, t) and (direction, id bits: -1 miss, sphere i, kFirstHitCuboidBase + cuboid j).  pickTile < 0:
+// records = rows x width x 2 float4; pickTile >= 0: only that tile, one workgroup, lane l of the tile at records[2 * l] (64 x 2 float4)
+constexpr int kFirstHitCuboidBase = 256; // PT_MAX_SPHERES (the winner numbering of ray_trace_t)
+hipError_t launch_first_hit(const FrameArgs &a, float4 *records, int pickTile, hipStream_t stream);
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 // the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);

@@ -163,6 +163,11 @@ struct pt_renderer {
     void *dRgba8 = nullptr;       // post-processed RGBA8 image of the tile (pt_present_rgba8)
     size_t rgba8Capacity = 0;     // in pixels
     size_t boundBytes = 0;
+    // First-hit query (pt_first_hit_render / pt_pick, pt_first_hit.hip): rows x width records of 32 bytes, allocated by the first
+    // pt_first_hit_render after a (re)size or (re)tiling and freed by the next one — never on the pt_render path; non-null = rendered
+    // since.  dPick: the 64 records of the one tile a pt_pick traces.
+    float4 *dFirstHit = nullptr;
+    float4 *dPick = nullptr;
 
     // hand-over audit (only allocated by the -DPT_AUDIT build, see pt_debug_hooks.hpp): side word per accumulation pixel + violation log
     unsigned long long *dAudit = nullptr;
@@ -312,5 +317,8 @@ int group_present_rgba8(pt_handle g, uint8_t *dst, size_t row_pitch_bytes);
 int group_present_async(pt_handle g, int slot);
 int group_result_device_ptr(pt_handle g, void **out_ptr, size_t *out_bytes);
 int group_timer_end(pt_handle g, float *out_ms);
+int free_first_hit(pt_handle h); // the first-hit records belong to a size and a tiling: whoever changes either drops them (streams joined)
+int group_first_hit_read(pt_handle g, void *dst, size_t row_pitch_bytes);
+int group_pick(pt_handle g, int x, int y, int frame_index, int *out_id, float *out_t, float *out_origin, float *out_dir);
 
 } // namespace ptimpl

@@ -299,6 +299,30 @@ public:
         Check(pt_present_rgba8(h_, img.data(), 0), h_);
         return img;
     }
+    // First-hit query — replaces the CPU ray caster of Gui.cs:223-233 -> MainWindow.RayTrace (MainWindow.cs:302-318) with the integrator's own
+    // ray: sample 0 of `frame` (lens and sub-pixel offset included).  Id: -1 miss, i = sphere i, PT_MAX_SPHERES + j = cuboid j; T = +inf on a miss.
+    struct FirstHitRecord {
+        float Origin[3], T, Direction[3];
+        int32_t Id;
+    };
+    static_assert(sizeof(FirstHitRecord) == 32, "one record of pt_first_hit_read");
+    // every pixel: width * height records, row 0 = bottom
+    std::vector<FirstHitRecord> FirstHit(int frame = 0) const
+    {
+        std::vector<FirstHitRecord> rec((size_t)width_ * height_);
+        Check(pt_first_hit_render(h_, frame), h_);
+        Check(pt_first_hit_read(h_, rec.data(), 0), h_);
+        return rec;
+    }
+    // one pixel (y = 0 is the bottom row)
+    FirstHitRecord Pick(int x, int y, int frame = 0) const
+    {
+        FirstHitRecord r{};
+        int id = -1;
+        Check(pt_pick(h_, x, y, frame, &id, &r.T, r.Origin, r.Direction), h_);
+        r.Id = id;
+        return r;
+    }
     // Accumulation checkpoint (same file as opentk-pathtracer_amd/checkpoint.py): 8-byte magic, int32 x 8
     // (width, height, y0, rows, band rows / world / rank, frame index), int32 x 2 (depth, spp), float x 2 (focal length,
     // aperture), then the raw RGBA32F rows.  The C++ mirror renders whole images (no tiling).

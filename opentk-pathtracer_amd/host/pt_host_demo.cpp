@@ -8,6 +8,9 @@
 //   pt_host_demo frame-loop <W> <H> <frames> <out.rgba8> <devices e.g. 0 or 0,0,0>
 //                      the frame loop of MainWindow.OnRenderFrame (:40-69) with the NON-BLOCKING present on one GPU or a group of
 //                      GPUs: Render(); PresentAsync(f % 3); PresentWait((f + 1) % 3); writes the last image shown + its frame index
+//   pt_host_demo pick <W> <H> <x> <y> [frame]
+//                      MainWindow.RayTrace for the pixel under the cursor (Gui.cs:223-233 -> MainWindow.cs:302-318), answered by the
+//                      integrator's own ray: prints the object and its distance, and focuses the thin lens on it (FocalLength = distance)
 //   pt_host_demo dump-scene <out.bin>            (no GPU needed: the 26,624-byte GameObjectsUBO image)
 //   pt_host_demo dump-camera <W> <H> <out.bin>   (no GPU needed: the 144-byte BasicDataUBO image)
 #include <cstdio>
@@ -65,6 +68,22 @@ int main(int argc, char **argv)
             std::printf("rendered %dx%d, %d samples/pixel\n", W, H, pathTracer.Samples());
             return 0;
         }
+        if (mode == "pick" && argc >= 6) {
+            int W = std::atoi(argv[2]), H = std::atoi(argv[3]), x = std::atoi(argv[4]), y = std::atoi(argv[5]), frame = argc > 6 ? std::atoi(argv[6]) : 0;
+            PathTracer pathTracer(nullptr, W, H, 13, 1, 20.0f, 0.14f); // (no environment needed: the query reads camera, scene and lens only)
+            LoadScene(pathTracer);
+            UploadCamera(pathTracer, camera, W, H);
+            // Gui.cs:223-233: `MainWindow.RayTrace(ray, out object, out t1, out t2)` on a click, then the object becomes the selection
+            PathTracer::FirstHitRecord hit = pathTracer.Pick(x, y, frame);
+            if (hit.Id < 0) {
+                std::printf("pixel (%d, %d): nothing\n", x, y);
+            } else {
+                std::printf("pixel (%d, %d): %s %d at distance %.6g\n", x, y, hit.Id < PT_MAX_SPHERES ? "sphere" : "cuboid",
+                            hit.Id < PT_MAX_SPHERES ? hit.Id : hit.Id - PT_MAX_SPHERES, (double)hit.T);
+                pathTracer.FocalLength(hit.T); // focus the lens on what was clicked
+            }
+            return 0;
+        }
         if (mode == "frame-loop" && argc == 7) {
             int W = std::atoi(argv[2]), H = std::atoi(argv[3]), frames = std::atoi(argv[4]);
             std::vector<int> devices;
@@ -117,7 +136,7 @@ int main(int argc, char **argv)
             std::printf("resumed at frame %d, now %d samples/pixel\n", restored, second.Samples());
             return 0;
         }
-        std::fprintf(stderr, "usage: pt_host_demo render W H frames out.f32 [rayDepth] [atmoSize] | frame-loop W H frames out.rgba8 devices | resume W H framesA framesB out.f32 ckpt shot.ppm | "
+        std::fprintf(stderr, "usage: pt_host_demo render W H frames out.f32 [rayDepth] [atmoSize] | pick W H x y [frame] | frame-loop W H frames out.rgba8 devices | resume W H framesA framesB out.f32 ckpt shot.ppm | "
                              "dump-scene out.bin | dump-camera W H out.bin\n");
         return 1;
     } catch (const std::exception &e) {

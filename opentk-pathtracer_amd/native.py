@@ -18,8 +18,8 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("MI355PT_LIB") or os.path.join(HERE, "libmi355pt.so")  # MI355PT_LIB: A/B tuning builds
 HEADER = os.path.join(REPO, "include", "mi355pt.h")
-SOURCES = ["pt_integrate_persistent.hip", "pt_integrate_multisample.hip", "pt_integrate_reference.hip", "pt_helper_kernels.hip", "mi355pt.cpp",
-           "mi355pt_multi.cpp"]
+SOURCES = ["pt_integrate_persistent.hip", "pt_integrate_multisample.hip", "pt_integrate_reference.hip", "pt_first_hit.hip", "pt_helper_kernels.hip",
+           "mi355pt.cpp", "mi355pt_multi.cpp"]
 # -ffp-contract=off / -fno-fast-math are part of the pt-f32 arithmetic contract (csrc/pt_math.hpp)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-shared",
                "-fvisibility=hidden"]
@@ -29,6 +29,7 @@ PT_MAX_IMAGE_DIM, PT_MAX_RAY_DEPTH, PT_MAX_SPP, PT_PRESENT_SLOTS = 32767, 4095, 
 PT_E_BAD_HANDLE, PT_E_BAD_ARGUMENT, PT_E_OUT_OF_RANGE, PT_E_NO_ENVIRONMENT, PT_E_HIP, PT_E_NO_DEVICE, PT_E_OOM = \
     -1, -2, -3, -4, -5, -6, -7
 PT_ENV_RGBA32F, PT_ENV_SRGB8_A8 = 0, 1
+PT_MAX_SPHERES, PT_MAX_CUBOIDS = 256, 64  # first-hit ids: sphere i = i, cuboid j = PT_MAX_SPHERES + j, miss = -1
 PT_ARITH_CONTRACT, PT_ARITH_REFERENCE = 0, 1  # pt_set_arithmetic, pt_atmosphere_set_arithmetic, pt_present_set_arithmetic
 
 
@@ -210,6 +211,10 @@ def load() -> C.CDLL:
         "pt_present_wait": [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), ip],
         "pt_present_bind_device_image": [vp, C.c_int, vp, C.c_size_t],
         "pt_present_set_arithmetic": [vp, C.c_int],
+        "pt_first_hit_render": [vp, C.c_int],
+        "pt_first_hit_read": [vp, vp, C.c_size_t],
+        "pt_first_hit_device_ptr": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
+        "pt_pick": [vp, C.c_int, C.c_int, C.c_int, ip, fp, fp, fp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

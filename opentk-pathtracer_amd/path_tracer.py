@@ -18,6 +18,11 @@ from . import native
 from .native import check
 
 
+# one record of pt_first_hit_read / pt_pick (include/mi355pt.h): 32 bytes
+FIRST_HIT_DTYPE = np.dtype([("origin", np.float32, 3), ("t", np.float32), ("dir", np.float32, 3), ("id", np.int32)])
+assert FIRST_HIT_DTYPE.itemsize == 32
+
+
 class EnvironmentMap:
     """A cube texture as the host would hand it to GL: 6 faces (+X,-X,+Y,-Y,+Z,-Z), RGBA32F or SRGB8_A8
     (MainWindow.cs:177-187)."""
@@ -268,6 +273,24 @@ class PathTracer:
         if mode not in (native.PT_ARITH_CONTRACT, native.PT_ARITH_REFERENCE):
             raise ValueError("mode must be native.PT_ARITH_CONTRACT or native.PT_ARITH_REFERENCE")
         check(self._lib.pt_present_set_arithmetic(self._h, mode), self._h)
+
+    # -- first-hit query (replaces the CPU ray caster of Gui.cs:223-233 -> MainWindow.RayTrace, MainWindow.cs:302-318)
+    def FirstHit(self, frame: int = 0) -> np.ndarray:
+        """pt_first_hit_render + pt_first_hit_read: per pixel the primary ray of sample 0 of `frame` and what it meets first, as a
+        (rows, Width) structured array (FIRST_HIT_DTYPE): origin (3,), t (+inf on a miss), dir (3,), id (-1 miss, sphere i = i,
+        cuboid j = native.PT_MAX_SPHERES + j).  Row 0 = image row y0.  Touches neither the image nor the frame counter."""
+        check(self._lib.pt_first_hit_render(self._h, frame), self._h)
+        out = np.empty((self.rows, self.Width), dtype=FIRST_HIT_DTYPE)
+        check(self._lib.pt_first_hit_read(self._h, out.ctypes.data_as(C.c_void_p), 0), self._h)
+        return out
+
+    def Pick(self, x: int, y: int, frame: int = 0):
+        """pt_pick: -> (id, t, origin (3,), dir (3,)) of image pixel (x, y) (y = 0 is the bottom row) for sample 0 of `frame`."""
+        i, t = C.c_int(), C.c_float()
+        o, d = np.empty(3, np.float32), np.empty(3, np.float32)
+        fp = C.POINTER(C.c_float)
+        check(self._lib.pt_pick(self._h, x, y, frame, C.byref(i), C.byref(t), o.ctypes.data_as(fp), d.ctypes.data_as(fp)), self._h)
+        return i.value, t.value, o, d
 
     def SetFrameBatch(self, max_frames: int) -> None:
         """Largest number of consecutive Render() calls one launch pipelines (1 = launch every frame at once)."""
