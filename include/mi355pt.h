@@ -329,6 +329,49 @@ PT_API int pt_first_hit_device_ptr(pt_handle h, void **out, size_t *bytes);
  * owns the row answers. */
 PT_API int pt_pick(pt_handle h, int x, int y, int frame_index, int *out_id, float *out_t, float out_origin[3], float out_dir[3]);
 
+/* ---- preview denoiser: guide buffers + an edge-avoiding a-trous filter ------------------------------------------ */
+
+/* The reference shows the raw accumulation image (src/MainWindow.cs:49-56 -> src/Render/ScreenEffect.cs:29-37), and resets it on
+ * every camera move, GUI edit and pick (MainWindow.cs:58-63): most of the time the user looks at frames 1..16, the noisiest images the
+ * renderer makes.  These calls filter the image for display WITHOUT touching it: pt_denoise_render writes, into buffers of the
+ * library, (1) a guide record per pixel from the integrator's own primary ray — 32 bytes = 8 words, rows like the image: words 0-2 hit
+ * position P = origin + direction * t (two roundings per component), word 3 id as int32 bits, words 4-6 shading normal N as RayTrace
+ * leaves it (not flipped when the origin lies inside the object; NaN on a cuboid's edges, as in the reference), word 7 t; id and t as
+ * in the first-hit record; miss: id -1, t +inf, P = N = 0 — and (2) `iterations` passes of a 5x5 a-trous wavelet filter (Dammertz et
+ * al. 2010) over the image's RGB, pass i with step 2^i, edge-stopping on id, normal, plane distance and tone-compressed luminance.
+ * The definition, operation by operation (it is reproducible bit for bit in binary32), is DESIGN.md section 3.5.
+ * SCOPE: single-GPU handles that own the whole image.  A group handle, or a handle under pt_set_tile (other than all rows) /
+ * pt_set_interleaved_tile, gets PT_E_BAD_ARGUMENT from all six calls: the filter reads up to 62 rows beyond a pixel's own.  With
+ * aperture > 0 the guides are lens-jittered like the first-hit record: the filter is specified, but only sharp at aperture 0. */
+
+/* Filter parameters of the pt_denoise_render calls that follow — a GUI slider's setter, like those MainWindow.cs:49-63 drives; the result
+ * is shown through ScreenEffect.cs:29-37.  iterations 0..6 (0 = the image is copied), sigma_color > 0 (luminance edge-stop; halves every
+ * pass), sigma_plane > 0 (plane-distance edge-stop, relative to the pixel's t), normal_log2_power 0..7 (the normal weight is max(0, Np.Nq)
+ * to the power 2^that).  Defaults 5, 0.5, 0.02, 5.  A non-finite sigma: PT_E_BAD_ARGUMENT; anything else outside its range:
+ * PT_E_OUT_OF_RANGE; the previous values stay in force then. */
+PT_API int pt_denoise_set_params(pt_handle h, int iterations, float sigma_color, float sigma_plane, int normal_log2_power);
+/* Denoise the image as it stands, for the present of MainWindow.cs:49-63 / ScreenEffect.cs:29-37: stream-ordered and asynchronous.
+ * Observes the image exactly as pt_postprocess_device does (pending frames are launched, an open frame-fed launch is closed, an
+ * abandoned hand-over is repaired first) and reads its RGB only; renders the guides for sample 0 of frame guide_frame_index in the
+ * CONTRACT arithmetic, then runs the passes.  Neither read nor written: the frame counter, the environment, the three arithmetic
+ * switches; never written: the accumulation image.  The buffers (rows x width x 64 bytes) are allocated by the first call after
+ * pt_set_size / pt_set_tile / pt_set_interleaved_tile, which free them (never by pt_render).  guide_frame_index < 0: PT_E_BAD_ARGUMENT. */
+PT_API int pt_denoise_render(pt_handle h, int guide_frame_index);
+/* The denoised image of the last pt_denoise_render as RGBA32F (alpha = 1), what MainWindow.cs:49-63 would hand to ScreenEffect.cs:29-37:
+ * blocks; row_pitch_bytes >= width*16, 0 = tightly packed.  PT_E_BAD_ARGUMENT when nothing was rendered since the last (re)size / (re)tiling. */
+PT_API int pt_denoise_read(pt_handle h, float *dst, size_t row_pitch_bytes);
+/* The guide records of the last pt_denoise_render (no counterpart in MainWindow.cs:49-63 / ScreenEffect.cs:29-37: the reference has no
+ * geometry buffers): blocks; 32 bytes per pixel, row_pitch_bytes >= width*32, 0 = tightly packed.  PT_E_BAD_ARGUMENT before the first render. */
+PT_API int pt_denoise_read_guides(pt_handle h, void *dst, size_t row_pitch_bytes);
+/* Device pointer + byte size of the denoised RGBA32F image (stream-ordered behind the pt_denoise_render that wrote it; valid until the
+ * next pt_denoise_render, resize or re-tiling), for a device-side present in place of MainWindow.cs:49-63 / ScreenEffect.cs:29-37.
+ * PT_E_BAD_ARGUMENT before the first render. */
+PT_API int pt_denoise_device_ptr(pt_handle h, void **out, size_t *bytes);
+/* pt_present_rgba8 of the denoised image: ScreenEffect.cs:29-37 (ACES + gamma, in the present arithmetic in force) over the result of
+ * the last pt_denoise_render instead of the raw image of MainWindow.cs:49-63; blocks; row_pitch_bytes >= width*4, 0 = tightly packed.
+ * PT_E_BAD_ARGUMENT before the first render. */
+PT_API int pt_denoise_present_rgba8(pt_handle h, uint8_t *dst, size_t row_pitch_bytes);
+
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);
 PT_API int pt_device_count(void);

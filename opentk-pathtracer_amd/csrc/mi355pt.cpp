@@ -295,6 +295,20 @@ int free_first_hit(pt_handle h)
     h->dFirstHit = nullptr;
     return PT_OK;
 }
+
+int free_denoise(pt_handle h)
+{
+    h->denoiseResult = -1;
+    if (!h->dGuides && !h->dDenoise[0] && !h->dDenoise[1]) return PT_OK;
+    PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_denoise_render may still write them)
+    if (h->dGuides) PT_HIP(h, hipFree(h->dGuides));
+    h->dGuides = nullptr;
+    for (float4 *&img : h->dDenoise) {
+        if (img) PT_HIP(h, hipFree(img));
+        img = nullptr;
+    }
+    return PT_OK;
+}
 } // namespace ptimpl
 
 namespace {
@@ -545,6 +559,9 @@ PT_API int pt_destroy(pt_handle h)
     if (h->dRgba8) (void)hipFree(h->dRgba8);
     if (h->dFirstHit) (void)hipFree(h->dFirstHit);
     if (h->dPick) (void)hipFree(h->dPick);
+    if (h->dGuides) (void)hipFree(h->dGuides);
+    if (h->dDenoise[0]) (void)hipFree(h->dDenoise[0]);
+    if (h->dDenoise[1]) (void)hipFree(h->dDenoise[1]);
     if (h->dTimeline) (void)hipFree(h->dTimeline);
     if (h->evBegin) (void)hipEventDestroy(h->evBegin);
     if (h->evEnd) (void)hipEventDestroy(h->evEnd);
@@ -565,6 +582,7 @@ PT_API int pt_set_size(pt_handle h, int width, int height)
     if (int rc = bind_device(h)) return rc;
     if (int rc = join_stripes(h)) return rc; // (the launches so far — and their hand-over repair passes — belong to the buffers as they are)
     if (int rc = ptimpl::free_first_hit(h)) return rc;
+    if (int rc = ptimpl::free_denoise(h)) return rc;
     h->width = width;
     h->height = height;
     h->y0 = 0;
@@ -586,6 +604,7 @@ PT_API int pt_set_tile(pt_handle h, int y0, int rows)
     if (int rc = bind_device(h)) return rc;
     if (int rc = join_stripes(h)) return rc; // (see pt_set_size)
     if (int rc = ptimpl::free_first_hit(h)) return rc;
+    if (int rc = ptimpl::free_denoise(h)) return rc;
     h->y0 = y0;
     h->rows = rows;
     h->bandRows = 0;
@@ -613,6 +632,7 @@ PT_API int pt_set_interleaved_tile(pt_handle h, int rank, int world, int band_ro
     if (rows <= 0) return fail(h, PT_E_BAD_ARGUMENT, "this rank owns no rows (image too small for world * band_rows)");
     if (int rc = join_stripes(h)) return rc; // (see pt_set_size)
     if (int rc = ptimpl::free_first_hit(h)) return rc;
+    if (int rc = ptimpl::free_denoise(h)) return rc;
     h->y0 = 0;
     h->rows = (int)rows;
     h->bandRows = band_rows;
@@ -2193,6 +2213,139 @@ PT_API int pt_pick(pt_handle h, int x, int y, int frame_index, int *out_id, floa
     if (out_origin) std::memcpy(out_origin, &rec[0], 12);
     if (out_dir) std::memcpy(out_dir, &rec[4], 12);
     return PT_OK;
+}
+
+// ---- preview denoiser (pt_denoise.hip): guides from the integrator's own primary ray + an edge-avoiding a-trous filter of
+// the accumulation image, for the first frames after the reset that every camera move and GUI edit causes (MainWindow.cs:49-63); the
+// result goes through the tone map of ScreenEffect.cs:29-37.  Reads the image (RGB), the camera shadow, the scene blob and the parameters;
+// touches neither the accumulation image, the frame counter, the environment nor an arithmetic switch.
+static int denoise_owner(pt_handle h)
+{
+    if (h->isGroup()) return fail(h, PT_E_BAD_ARGUMENT, "the denoiser is not available on a group handle");
+    if (h->rows != h->height || h->bandRows != 0)
+        return fail(h, PT_E_BAD_ARGUMENT, "the denoiser needs a handle that owns the whole image (pt_set_tile / pt_set_interleaved_tile in force)");
+    return PT_OK;
+}
+
+// stage < -1: everything; -1: the guides only; i >= 0: pass i only (pt_debug_denoise_stage, for timing)
+static int denoise_run(pt_handle h, int guide_frame_index, int stage)
+{
+    if (int rc = bind_device(h)) return rc;
+    // (the preamble of pt_postprocess_device: pending frames are launched, an open frame-fed launch is closed, an abandoned hand-over is repaired)
+    if (int rc = join_stripes(h)) return rc;
+    const size_t pixels = h->tilePixels();
+    if (!h->dGuides) PT_HIP(h, hipMalloc((void **)&h->dGuides, pixels * 2 * sizeof(float4)));
+    for (float4 *&img : h->dDenoise)
+        if (!img) PT_HIP(h, hipMalloc((void **)&img, pixels * sizeof(float4)));
+    if (stage < 0) {
+        pt::FrameArgs a;
+        first_hit_args(h, a, guide_frame_index);
+        PT_HIP(h, pt::launch_guides(a, h->dGuides, h->stream));
+        if (stage == -1) return PT_OK;
+    }
+    const int n = h->denoiseIterations;
+    if (n == 0 && stage < 0) PT_HIP(h, pt::launch_denoise_copy(h->accum(), h->dDenoise[0], pixels, h->stream));
+    for (int i = 0; i < n; i++) {
+        if (stage >= 0 && i != stage) continue;
+        pt::AtrousArgs t;
+        t.colIn = i == 0 ? h->accum() : h->dDenoise[(i - 1) & 1];
+        t.guides = h->dGuides;
+        t.colOut = h->dDenoise[i & 1];
+        t.width = h->width;
+        t.height = h->rows;
+        t.step = 1 << i;
+        t.invSigma = 1.0f / (h->denoiseSigmaColor * std::ldexp(1.0f, -i));
+        t.sigmaPlane = h->denoiseSigmaPlane;
+        t.normalPower = h->denoiseNormalPower;
+        PT_HIP(h, pt::launch_atrous(t, h->stream));
+    }
+    if (stage < 0) h->denoiseResult = n == 0 ? 0 : (n - 1) & 1;
+    return PT_OK;
+}
+
+PT_API int pt_denoise_set_params(pt_handle h, int iterations, float sigma_color, float sigma_plane, int normal_log2_power)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    if (!std::isfinite(sigma_color) || !std::isfinite(sigma_plane)) return fail(h, PT_E_BAD_ARGUMENT, "sigma_color and sigma_plane must be finite");
+    if (iterations < 0 || iterations > 6 || normal_log2_power < 0 || normal_log2_power > 7 || !(sigma_color > 0.0f) || !(sigma_plane > 0.0f))
+        return fail(h, PT_E_OUT_OF_RANGE, "iterations 0..6, normal_log2_power 0..7, sigma_color > 0, sigma_plane > 0");
+    h->denoiseIterations = iterations; // (read by the next pt_denoise_render; what is queued already took its values)
+    h->denoiseSigmaColor = sigma_color;
+    h->denoiseSigmaPlane = sigma_plane;
+    h->denoiseNormalPower = normal_log2_power;
+    return PT_OK;
+}
+
+PT_API int pt_denoise_render(pt_handle h, int guide_frame_index)
+{
+    PT_CHECK_HANDLE(h);
+    if (guide_frame_index < 0) return fail(h, PT_E_BAD_ARGUMENT, "guide_frame_index must be >= 0");
+    if (int rc = denoise_owner(h)) return rc;
+    return denoise_run(h, guide_frame_index, -2);
+}
+
+static int denoise_rendered(pt_handle h)
+{
+    if (int rc = denoise_owner(h)) return rc;
+    if (h->denoiseResult < 0) return fail(h, PT_E_BAD_ARGUMENT, "no pt_denoise_render since the last pt_set_size / pt_set_tile / pt_set_interleaved_tile");
+    return bind_device(h);
+}
+
+static int denoise_copy_out(pt_handle h, void *dst, size_t row_pitch_bytes, const void *src, size_t bytesPerPixel)
+{
+    if (!dst) return fail(h, PT_E_BAD_ARGUMENT, "dst == NULL");
+    const size_t rowBytes = (size_t)h->width * bytesPerPixel;
+    if (row_pitch_bytes == 0) row_pitch_bytes = rowBytes;
+    if (row_pitch_bytes < rowBytes) return fail(h, PT_E_BAD_ARGUMENT, "row pitch smaller than a row");
+    PT_HIP(h, hipMemcpy2DAsync(dst, row_pitch_bytes, src, rowBytes, rowBytes, (size_t)h->rows, hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(h, hipStreamSynchronize(h->stream));
+    return PT_OK;
+}
+
+PT_API int pt_denoise_read(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->dDenoise[h->denoiseResult], 16);
+}
+
+PT_API int pt_denoise_read_guides(pt_handle h, void *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->dGuides, 32);
+}
+
+PT_API int pt_denoise_device_ptr(pt_handle h, void **out, size_t *bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    if (out) *out = h->dDenoise[h->denoiseResult];
+    if (bytes) *bytes = h->tilePixels() * sizeof(float4);
+    return PT_OK;
+}
+
+PT_API int pt_denoise_present_rgba8(pt_handle h, uint8_t *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    if (!dst) return fail(h, PT_E_BAD_ARGUMENT, "dst == NULL");
+    if (row_pitch_bytes != 0 && row_pitch_bytes < (size_t)h->width * 4) return fail(h, PT_E_BAD_ARGUMENT, "row pitch smaller than a row");
+    if (int rc = join_stripes(h)) return rc; // (dRgba8 is shared with pt_present_rgba8 / pt_postprocess_device: same ordering as theirs)
+    if (int rc = ensure_rgba8(h)) return rc;
+    PT_HIP(h, ptimpl::launch_tone_map(h->presentArithmetic, h->dDenoise[h->denoiseResult], h->dRgba8, h->tilePixels(), h->stream));
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->dRgba8, 4);
+}
+
+// Timing aid (not declared in the public header): one stage of pt_denoise_render on its own — stage -1 = the guide kernel, i >= 0 = pass i
+// between the buffers a full render uses (a pt_denoise_render must have run; the result it left is overwritten with a partial one).
+extern "C" __attribute__((visibility("default"))) int pt_debug_denoise_stage(pt_handle h, int guide_frame_index, int stage)
+{
+    PT_CHECK_HANDLE(h);
+    if (guide_frame_index < 0 || stage < -1 || stage >= h->denoiseIterations) return fail(h, PT_E_BAD_ARGUMENT, "stage must be -1 .. iterations - 1");
+    if (int rc = denoise_rendered(h)) return rc;
+    return denoise_run(h, guide_frame_index, stage);
 }
 
 // Tuning aid (not declared in the public header): per-wavefront timestamps of the next persistent-kernel launches.

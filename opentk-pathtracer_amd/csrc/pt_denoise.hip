@@ -1,0 +1,189 @@
+// pt_denoise.hip — the preview denoiser (pt_denoise_render): guide buffers from the integrator's own primary ray, and an edge-avoiding
+// 5x5 a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination
+// Filtering", HPG 2010) with edge-stopping on object id, shading normal, plane distance and tone-compressed luminance.  The reference
+// has no counterpart: it shows the raw accumulation image, which every camera move, GUI edit and pick resets (MainWindow.cs:49-63).
+// The filter's definition is DESIGN.md section 3.5, restated in numpy float32 by tests/denoise_reference.py; the kernels reproduce that
+// restatement bit for bit, so every expression below is a fixed sequence of single IEEE binary32 + - * / operations, comparisons and
+// selects: nothing fused (-ffp-contract=off -fno-fast-math), no transcendentals, no fminf / fmaxf (x > 0 ? x : 0 sends NaN to 0 the way
+// np.where does), `/` = the correctly rounded divide (v_div_scale / v_div_fmas / v_div_fixup).
+// Build flags: those of the library.
+#include "pt_kernel_common.hpp"
+
+namespace pt {
+
+// ---------------------------------------------------------------------------------------------- guides
+// Two float4 per pixel, rows like the image: G0 = (P.xyz, id bits), G1 = (N.xyz, t).  id and t as pt_first_hit_kernel writes them
+// (the same ray: sample 0 of a.frame, the same ray_trace, the same id table in the Albedo.x slot); N = Hit::normal as ray_trace leaves
+// it (compute.glsl:239-240,252-253: not flipped for FromInside); P = origin + direction * t in two roundings per component — the hit
+// position of compute.glsl:238,251 without the contract's fused multiply-add, so that a host restates it from a first-hit record.
+// Miss: id = -1, t = +inf, P = N = 0.  Shape of pt_first_hit_kernel: one wavefront per 8x8 tile, 256-thread workgroups.
+__global__ __launch_bounds__(256) void pt_guides_kernel(const FrameArgs a, float4 *guides)
+{
+    SceneLds sc = stage_scene(a); // (geometry only: the launch sets materialsInLds = 0, envFormat = 0, gridLdsBytes = 0)
+    const int tid = threadIdx.x;
+    const int ns = a.numSpheres, nc = a.numCuboids;
+    float4 *ids = g_lds + scene_lds_bytes(ns, nc, 0, false) / sizeof(float4);
+    for (int i = tid; i < ns + nc; i += 256) ids[4 * i] = make_float4((float)(i < ns ? i : kFirstHitCuboidBase + (i - ns)), 0.0f, 0.0f, 0.0f);
+    __syncthreads();
+    sc.mat = ids;
+    const int b = xcd_band_id(blockIdx.x, gridDim.x);
+    const int wave = tid >> 6, lane = tid & 63;
+    const int tile = b * 4 + wave;
+    if (tile >= a.tilesX * a.tilesY) return;
+    const int tx = tile % a.tilesX, ty = tile / a.tilesX;
+    const int px = tx * 8 + (lane & 7);
+    const int ly = ty * 8 + (lane >> 3);
+    if (px >= a.width || ly >= a.rows) return;
+#ifdef PT_PROFILE
+    unsigned long long prof_dummy[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    uint32_t seed = pixel_seed(px, global_row(a, ly), a.frame); // compute.glsl:106
+    v3 ro, rd;
+    primary_ray(a, px, global_row(a, ly), seed, ro, rd);        // :113-121, sample 0
+    Hit h;
+    const bool hit = ray_trace(sc, ns, nc, ro, rd, h PROF_DUMMY); // :226-258
+    float4 g0 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+    float4 g1 = make_float4(0.0f, 0.0f, 0.0f, __builtin_inff());
+    if (hit) {
+        g0 = make_float4(rd.x * h.T + ro.x, rd.y * h.T + ro.y, rd.z * h.T + ro.z, __int_as_float((int)h.m.albedo.x));
+        g1 = make_float4(h.normal.x, h.normal.y, h.normal.z, h.T);
+    }
+    const size_t at = (size_t)ly * a.width + px;
+    guides[2 * at] = g0;
+    guides[2 * at + 1] = g1;
+}
+
+hipError_t launch_guides(const FrameArgs &args, float4 *guides, hipStream_t stream)
+{
+    FrameArgs a = args;
+    a.materialsInLds = 0; // (stage_scene: geometry only — the material table is the kernel's id table)
+    a.gridLdsBytes = 0;
+    a.envFormat = 0;      // (no environment is read: no sRGB table is staged)
+    if (a.tilesX < 1 || a.tilesY < 1) return hipErrorInvalidValue;
+    const int tiles = a.tilesX * a.tilesY;
+    const size_t lds = scene_lds_bytes(a.numSpheres, a.numCuboids, 0, false) + (size_t)(a.numSpheres + a.numCuboids) * 4 * sizeof(float4);
+    hipLaunchKernelGGL(pt_guides_kernel, dim3((tiles + 3) / 4), dim3(256), lds, stream, a, guides);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- a-trous pass
+// u(c) = l / (1 + l), l = 0.2126 r + 0.7152 g + 0.0722 b (left to right): the luminance the colour weight compares, compressed to [0, 1)
+PT_DEV float dn_u(float r, float g, float b)
+{
+    const float l = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+    return l / (1.0f + l);
+}
+
+// One pass, one pixel per lane.  S = 1, 2: the step; the 16x16 tile plus a halo of 2 S pixels — G0, G1 and (r, g, b, u) = 48 bytes per
+// pixel — is staged into LDS (S = 2: 24 x 24 x 48 = 27,648 bytes), u evaluated once per staged pixel instead of once per tap.
+// S = 0: any step (a.step), 64x4 tiles, every tap read from memory — a wavefront is 64 adjacent pixels of one row, so each tap is one
+// coalesced 1 KB load per array; G0 first, G1 and the colour only where the id matches.
+template <int S>
+__global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
+{
+    constexpr int TX = S ? 16 : 64, TY = S ? 16 : 4, HALO = 2 * S, LW = TX + 2 * HALO, LH = TY + 2 * HALO;
+    __shared__ float4 sG0[S ? LW * LH : 1], sG1[S ? LW * LH : 1], sC[S ? LW * LH : 1];
+    const int tid = threadIdx.x, lx = tid % TX, ly = tid / TX;
+    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+    const int px = x0 + lx, py = y0 + ly;
+    const int step = S ? S : a.step;
+    if constexpr (S != 0) {
+        for (int i = tid; i < LW * LH; i += 256) {
+            const int qx = x0 - HALO + i % LW, qy = y0 - HALO + i / LW;
+            if (qx >= 0 && qx < a.width && qy >= 0 && qy < a.height) { // (cells outside the image are never read: their taps are skipped)
+                const size_t at = (size_t)qy * a.width + qx;
+                float4 c = a.colIn[at];
+                c.w = dn_u(c.x, c.y, c.z);
+                sG0[i] = a.guides[2 * at];
+                sG1[i] = a.guides[2 * at + 1];
+                sC[i] = c;
+            }
+        }
+        __syncthreads();
+    }
+    if (px >= a.width || py >= a.height) return;
+    const size_t center = (size_t)py * a.width + px;
+    const int lc = (ly + HALO) * LW + lx + HALO;
+    const float4 g0p = S ? sG0[lc] : a.guides[2 * center];
+    const float4 g1p = S ? sG1[lc] : a.guides[2 * center + 1];
+    float4 cp = S ? sC[lc] : a.colIn[center];
+    const int idp = __float_as_int(g0p.w);
+    float4 out = make_float4(cp.x, cp.y, cp.z, 1.0f);
+    if (idp != -1) {
+        const float up = S ? cp.w : dn_u(cp.x, cp.y, cp.z);
+        const float planeDen = a.sigmaPlane * g1p.w;
+        float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f;
+#pragma unroll
+        for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; dx++) {
+                const float kx = dx == 0 ? 0.375f : (dx == 1 || dx == -1 ? 0.25f : 0.0625f);
+                const float ky = dy == 0 ? 0.375f : (dy == 1 || dy == -1 ? 0.25f : 0.0625f);
+                const float hk = kx * ky; // (exact)
+                const int qx = px + step * dx, qy = py + step * dy;
+                if (qx < 0 || qx >= a.width || qy < 0 || qy >= a.height) continue;
+                const size_t at = (size_t)qy * a.width + qx;
+                const int lq = lc + dy * S * LW + dx * S;
+                const float4 g0q = S ? sG0[lq] : a.guides[2 * at];
+                if (__float_as_int(g0q.w) != idp) continue;
+                const float4 g1q = S ? sG1[lq] : a.guides[2 * at + 1];
+                const float4 cq = S ? sC[lq] : a.colIn[at];
+                const float d = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
+                float wn = d > 0.0f ? d : 0.0f;
+                for (int k = 0; k < a.normalPower; k++) wn = wn * wn;
+                const float ex = g0q.x - g0p.x, ey = g0q.y - g0p.y, ez = g0q.z - g0p.z;
+                const float e = (g1p.x * ex + g1p.y * ey) + g1p.z * ez;
+                const float r = e / planeDen;
+                const float z = 1.0f - r * r;
+                const float wz = z > 0.0f ? z : 0.0f;
+                const float uq = S ? cq.w : dn_u(cq.x, cq.y, cq.z);
+                const float da = (uq - up) * a.invSigma;
+                const float c1 = 1.0f - da * da;
+                const float c2 = c1 > 0.0f ? c1 : 0.0f;
+                const float wc = c2 * c2;
+                const float w = ((hk * wn) * wz) * wc;
+                W = W + w;
+                Sr = Sr + w * cq.x;
+                Sg = Sg + w * cq.y;
+                Sb = Sb + w * cq.z;
+            }
+        }
+        if (W > 0.0f) out = make_float4(Sr / W, Sg / W, Sb / W, 1.0f);
+    }
+    a.colOut[center] = out;
+}
+
+hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream)
+{
+    if (a.width < 1 || a.height < 1 || a.step < 1) return hipErrorInvalidValue;
+    if (a.step <= 2) {
+        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+        if (a.step == 1) hipLaunchKernelGGL(pt_atrous_kernel<1>, grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(pt_atrous_kernel<2>, grid, dim3(256), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL(pt_atrous_kernel<0>, dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+// iterations = 0: the image itself — RGB copied, alpha = the 1 every observer of the image sees (inside a launch chain alpha carries frame tags)
+__global__ void pt_denoise_copy_kernel(const float4 *in, float4 *out, size_t n)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        const float4 c = in[i];
+        out[i] = make_float4(c.x, c.y, c.z, 1.0f);
+    }
+}
+
+hipError_t launch_denoise_copy(const float4 *in, float4 *out, size_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(pt_denoise_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, in, out, n);
+    return hipGetLastError();
+}
+
+} // namespace pt

@@ -225,6 +225,22 @@ hipError_t launch_repair_done(unsigned int *abandonWord, unsigned int *queueMain
 // records = rows x width x 2 float4; pickTile >= 0: only that tile, one workgroup, lane l of the tile at records[2 * l] (64 x 2 float4)
 constexpr int kFirstHitCuboidBase = 256; // PT_MAX_SPHERES (the winner numbering of ray_trace_t)
 hipError_t launch_first_hit(const FrameArgs &a, float4 *records, int pickTile, hipStream_t stream);
+// the preview denoiser (pt_denoise.hip).  Guides: per pixel of the launch (fields as for launch_first_hit) two float4 —
+// (P.xyz, id bits) and (N.xyz, t), id / t as the first-hit record's.
+hipError_t launch_guides(const FrameArgs &a, float4 *guides, hipStream_t stream);
+// one a-trous pass colIn -> colOut over a width x height image (compact rows); colIn's alpha is not read, colOut's is 1
+struct AtrousArgs {
+    const float4 *colIn;
+    const float4 *guides;
+    float4 *colOut;
+    int width, height;
+    int step;         // 2^i for pass i
+    float invSigma;   // 1.0f / (sigma_color * 2^-i), computed by the host in binary32
+    float sigmaPlane;
+    int normalPower;  // the normal weight is squared this many times
+};
+hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream);
+hipError_t launch_denoise_copy(const float4 *in, float4 *out, size_t pixels, hipStream_t stream); // out = (in.rgb, 1)
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 // the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);

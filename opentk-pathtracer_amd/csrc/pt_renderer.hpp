@@ -168,6 +168,14 @@ struct pt_renderer {
     // since.  dPick: the 64 records of the one tile a pt_pick traces.
     float4 *dFirstHit = nullptr;
     float4 *dPick = nullptr;
+    // Preview denoiser (pt_denoise_render, pt_denoise.hip): rows x width guide records of 32 bytes and the two ping-pong images of the
+    // a-trous passes, allocated by the first pt_denoise_render after a (re)size or (re)tiling and freed by the next one — never on the
+    // pt_render path.  denoiseResult: which of the two images holds the last result (-1 = nothing rendered since).
+    float4 *dGuides = nullptr;
+    float4 *dDenoise[2] = {nullptr, nullptr};
+    int denoiseResult = -1;
+    int denoiseIterations = 5, denoiseNormalPower = 5; // pt_denoise_set_params
+    float denoiseSigmaColor = 0.5f, denoiseSigmaPlane = 0.02f;
 
     // hand-over audit (only allocated by the -DPT_AUDIT build, see pt_debug_hooks.hpp): side word per accumulation pixel + violation log
     unsigned long long *dAudit = nullptr;
@@ -318,6 +326,7 @@ int group_present_async(pt_handle g, int slot);
 int group_result_device_ptr(pt_handle g, void **out_ptr, size_t *out_bytes);
 int group_timer_end(pt_handle g, float *out_ms);
 int free_first_hit(pt_handle h); // the first-hit records belong to a size and a tiling: whoever changes either drops them (streams joined)
+int free_denoise(pt_handle h);   // ... and so do the denoiser's guides and images
 int group_first_hit_read(pt_handle g, void *dst, size_t row_pitch_bytes);
 int group_pick(pt_handle g, int x, int y, int frame_index, int *out_id, float *out_t, float *out_origin, float *out_dir);
 

@@ -323,6 +323,40 @@ public:
         r.Id = id;
         return r;
     }
+    // Preview denoiser — the image of MainWindow.cs:49-56 filtered for display, for the first frames after a ResetRenderer():
+    // guides from sample 0 of `frame` + an edge-avoiding a-trous filter; the image and the frame counter are not touched.
+    struct GuideRecord {
+        float Position[3];
+        int32_t Id;
+        float Normal[3], T;
+    };
+    static_assert(sizeof(GuideRecord) == 32, "one record of pt_denoise_read_guides");
+    void SetDenoise(int iterations = 5, float sigmaColor = 0.5f, float sigmaPlane = 0.02f, int normalLog2Power = 5)
+    {
+        Check(pt_denoise_set_params(h_, iterations, sigmaColor, sigmaPlane, normalLog2Power), h_);
+    }
+    // the denoised RGBA32F image (alpha = 1), row 0 = bottom
+    std::vector<float> Denoise(int frame = 0) const
+    {
+        std::vector<float> img((size_t)width_ * height_ * 4);
+        Check(pt_denoise_render(h_, frame), h_);
+        Check(pt_denoise_read(h_, img.data(), 0), h_);
+        return img;
+    }
+    // the guide records of the last Denoise()
+    std::vector<GuideRecord> DenoiseGuides() const
+    {
+        std::vector<GuideRecord> rec((size_t)width_ * height_);
+        Check(pt_denoise_read_guides(h_, rec.data(), 0), h_);
+        return rec;
+    }
+    // ScreenEffect.Render (src/Render/ScreenEffect.cs:29-37) of the last Denoise() instead of `Result`
+    std::vector<uint8_t> PresentDenoised() const
+    {
+        std::vector<uint8_t> img((size_t)width_ * height_ * 4);
+        Check(pt_denoise_present_rgba8(h_, img.data(), 0), h_);
+        return img;
+    }
     // Accumulation checkpoint (same file as opentk-pathtracer_amd/checkpoint.py): 8-byte magic, int32 x 8
     // (width, height, y0, rows, band rows / world / rank, frame index), int32 x 2 (depth, spp), float x 2 (focal length,
     // aperture), then the raw RGBA32F rows.  The C++ mirror renders whole images (no tiling).

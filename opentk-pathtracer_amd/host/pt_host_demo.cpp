@@ -11,6 +11,9 @@
 //   pt_host_demo pick <W> <H> <x> <y> [frame]
 //                      MainWindow.RayTrace for the pixel under the cursor (Gui.cs:223-233 -> MainWindow.cs:302-318), answered by the
 //                      integrator's own ray: prints the object and its distance, and focuses the thin lens on it (FocalLength = distance)
+//   pt_host_demo denoise <W> <H> <frames> <out.rgba8> [iterations]
+//                      the first frames after a ResetRenderer() (MainWindow.cs:58-63), shown through the preview denoiser: N x Render(),
+//                      then Denoise() + PresentDenoised() in place of ScreenEffect.Render(PathTracer.Result) (MainWindow.cs:49-56)
 //   pt_host_demo dump-scene <out.bin>            (no GPU needed: the 26,624-byte GameObjectsUBO image)
 //   pt_host_demo dump-camera <W> <H> <out.bin>   (no GPU needed: the 144-byte BasicDataUBO image)
 #include <cstdio>
@@ -84,6 +87,24 @@ int main(int argc, char **argv)
             }
             return 0;
         }
+        if (mode == "denoise" && argc >= 6) {
+            int W = std::atoi(argv[2]), H = std::atoi(argv[3]), frames = std::atoi(argv[4]);
+            PathTracer pathTracer(nullptr, W, H, 13, 1, 20.0f, 0.0f); // (aperture 0: the guides are sharp)
+            AtmosphericScatterer atmosphericScatterer(pathTracer, 64);
+            atmosphericScatterer.Render();
+            LoadScene(pathTracer);
+            UploadCamera(pathTracer, camera, W, H);
+            if (argc > 6) pathTracer.SetDenoise(std::atoi(argv[6]));
+            std::vector<uint8_t> shown;
+            for (int i = 0; i < frames; i++) {
+                pathTracer.Render();                  // OnRenderFrame, MainWindow.cs:49
+                pathTracer.Denoise(0);                // (guides of frame 0: the camera has not moved since the reset)
+                shown = pathTracer.PresentDenoised(); // :51 — ScreenEffect.Render of the filtered image; `Result` keeps accumulating untouched
+            }
+            write_file(argv[5], shown.data(), shown.size());
+            std::printf("showed %dx%d denoised, %d samples/pixel\n", W, H, pathTracer.Samples());
+            return 0;
+        }
         if (mode == "frame-loop" && argc == 7) {
             int W = std::atoi(argv[2]), H = std::atoi(argv[3]), frames = std::atoi(argv[4]);
             std::vector<int> devices;
@@ -136,7 +157,7 @@ int main(int argc, char **argv)
             std::printf("resumed at frame %d, now %d samples/pixel\n", restored, second.Samples());
             return 0;
         }
-        std::fprintf(stderr, "usage: pt_host_demo render W H frames out.f32 [rayDepth] [atmoSize] | pick W H x y [frame] | frame-loop W H frames out.rgba8 devices | resume W H framesA framesB out.f32 ckpt shot.ppm | "
+        std::fprintf(stderr, "usage: pt_host_demo render W H frames out.f32 [rayDepth] [atmoSize] | pick W H x y [frame] | denoise W H frames out.rgba8 [iterations] | frame-loop W H frames out.rgba8 devices | resume W H framesA framesB out.f32 ckpt shot.ppm | "
                              "dump-scene out.bin | dump-camera W H out.bin\n");
         return 1;
     } catch (const std::exception &e) {

@@ -18,8 +18,8 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("MI355PT_LIB") or os.path.join(HERE, "libmi355pt.so")  # MI355PT_LIB: A/B tuning builds
 HEADER = os.path.join(REPO, "include", "mi355pt.h")
-SOURCES = ["pt_integrate_persistent.hip", "pt_integrate_multisample.hip", "pt_integrate_reference.hip", "pt_first_hit.hip", "pt_helper_kernels.hip",
-           "mi355pt.cpp", "mi355pt_multi.cpp"]
+SOURCES = ["pt_integrate_persistent.hip", "pt_integrate_multisample.hip", "pt_integrate_reference.hip", "pt_first_hit.hip", "pt_denoise.hip",
+           "pt_helper_kernels.hip", "mi355pt.cpp", "mi355pt_multi.cpp"]
 # -ffp-contract=off / -fno-fast-math are part of the pt-f32 arithmetic contract (csrc/pt_math.hpp)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-shared",
                "-fvisibility=hidden"]
@@ -215,6 +215,12 @@ def load() -> C.CDLL:
         "pt_first_hit_read": [vp, vp, C.c_size_t],
         "pt_first_hit_device_ptr": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
         "pt_pick": [vp, C.c_int, C.c_int, C.c_int, ip, fp, fp, fp],
+        "pt_denoise_set_params": [vp, C.c_int, C.c_float, C.c_float, C.c_int],
+        "pt_denoise_render": [vp, C.c_int],
+        "pt_denoise_read": [vp, fp, C.c_size_t],
+        "pt_denoise_read_guides": [vp, vp, C.c_size_t],
+        "pt_denoise_device_ptr": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
+        "pt_denoise_present_rgba8": [vp, C.POINTER(C.c_uint8), C.c_size_t],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -270,3 +276,12 @@ def debug_handover_stats(handle) -> dict:
     out = (C.c_uint * 4)()
     check(L.pt_debug_handover_stats(handle, out), handle)
     return {"pairs_repaired": int(out[0]), "inconsistent": int(out[1]), "joins_with_repairs": int(out[2]), "flag_seen": int(out[3])}
+
+
+def debug_denoise_stage(handle, frame: int, stage: int) -> None:
+    """One stage of pt_denoise_render on its own, for timing (pt_debug_denoise_stage — exported, not in the public header): stage -1 = the
+    guide kernel, i >= 0 = pass i.  A pt_denoise_render must have run; the result it left is overwritten with a partial one."""
+    L = load()
+    L.pt_debug_denoise_stage.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.pt_debug_denoise_stage.restype = C.c_int
+    check(L.pt_debug_denoise_stage(handle, frame, stage), handle)

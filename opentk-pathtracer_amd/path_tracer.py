@@ -21,6 +21,9 @@ from .native import check
 # one record of pt_first_hit_read / pt_pick (include/mi355pt.h): 32 bytes
 FIRST_HIT_DTYPE = np.dtype([("origin", np.float32, 3), ("t", np.float32), ("dir", np.float32, 3), ("id", np.int32)])
 assert FIRST_HIT_DTYPE.itemsize == 32
+# one guide record of pt_denoise_read_guides (include/mi355pt.h): 32 bytes; id and t as in FIRST_HIT_DTYPE
+GUIDE_DTYPE = np.dtype([("pos", np.float32, 3), ("id", np.int32), ("normal", np.float32, 3), ("t", np.float32)])
+assert GUIDE_DTYPE.itemsize == 32
 
 
 class EnvironmentMap:
@@ -291,6 +294,32 @@ class PathTracer:
         fp = C.POINTER(C.c_float)
         check(self._lib.pt_pick(self._h, x, y, frame, C.byref(i), C.byref(t), o.ctypes.data_as(fp), d.ctypes.data_as(fp)), self._h)
         return i.value, t.value, o, d
+
+    # -- preview denoiser (the image of MainWindow.cs:49-56 filtered for display)
+    def SetDenoise(self, iterations: int = 5, sigma_color: float = 0.5, sigma_plane: float = 0.02, normal_log2_power: int = 5) -> None:
+        """pt_denoise_set_params: a-trous passes (0..6), luminance and plane-distance edge-stops (> 0), log2 of the normal weight's power (0..7)."""
+        check(self._lib.pt_denoise_set_params(self._h, iterations, sigma_color, sigma_plane, normal_log2_power), self._h)
+
+    def Denoise(self, frame: int = 0) -> np.ndarray:
+        """pt_denoise_render + pt_denoise_read: the image as it stands, filtered with guides from sample 0 of `frame`, as (rows, Width, 4)
+        float32 (alpha = 1).  Touches neither the image nor the frame counter.  Single-GPU handles that own the whole image."""
+        check(self._lib.pt_denoise_render(self._h, frame), self._h)
+        out = np.empty((self.rows, self.Width, 4), dtype=np.float32)
+        check(self._lib.pt_denoise_read(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
+        return out
+
+    def DenoiseGuides(self) -> np.ndarray:
+        """pt_denoise_read_guides: the guide records of the last Denoise as a (rows, Width) structured array (GUIDE_DTYPE): pos (3,), id,
+        normal (3,), t; a miss has id -1, t +inf, pos = normal = 0."""
+        out = np.empty((self.rows, self.Width), dtype=GUIDE_DTYPE)
+        check(self._lib.pt_denoise_read_guides(self._h, out.ctypes.data_as(C.c_void_p), 0), self._h)
+        return out
+
+    def PresentDenoised(self) -> np.ndarray:
+        """pt_denoise_present_rgba8: the result of the last Denoise through the tone map Present applies, as (rows, Width, 4) uint8."""
+        out = np.empty((self.rows, self.Width, 4), dtype=np.uint8)
+        check(self._lib.pt_denoise_present_rgba8(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8)), 0), self._h)
+        return out
 
     def SetFrameBatch(self, max_frames: int) -> None:
         """Largest number of consecutive Render() calls one launch pipelines (1 = launch every frame at once)."""
