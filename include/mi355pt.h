@@ -341,7 +341,7 @@ PT_API int pt_pick(pt_handle h, int x, int y, int frame_index, int *out_id, floa
  * al. 2010) over the image's RGB, pass i with step 2^i, edge-stopping on id, normal, plane distance and tone-compressed luminance.
  * The definition, operation by operation (it is reproducible bit for bit in binary32), is DESIGN.md section 3.5.
  * SCOPE: single-GPU handles that own the whole image.  A group handle, or a handle under pt_set_tile (other than all rows) /
- * pt_set_interleaved_tile, gets PT_E_BAD_ARGUMENT from all six calls: the filter reads up to 62 rows beyond a pixel's own.  With
+ * pt_set_interleaved_tile, gets PT_E_BAD_ARGUMENT from all of these calls: the filter reads up to 62 rows beyond a pixel's own.  With
  * aperture > 0 the guides are lens-jittered like the first-hit record: the filter is specified, but only sharp at aperture 0. */
 
 /* Filter parameters of the pt_denoise_render calls that follow — a GUI slider's setter, like those MainWindow.cs:49-63 drives; the result
@@ -371,6 +371,26 @@ PT_API int pt_denoise_device_ptr(pt_handle h, void **out, size_t *bytes);
  * the last pt_denoise_render instead of the raw image of MainWindow.cs:49-63; blocks; row_pitch_bytes >= width*4, 0 = tightly packed.
  * PT_E_BAD_ARGUMENT before the first render. */
 PT_API int pt_denoise_present_rgba8(pt_handle h, uint8_t *dst, size_t row_pitch_bytes);
+
+/* Modes of the luminance edge-stop (pt_denoise_set_mode).  FIXED: one width for the whole image, sigma_color, halved every pass — the
+ * filter above, bit for bit.  VARIANCE: the stop of every pixel is sigma_variance standard deviations of that pixel's own noise (the
+ * variance-guided edge stop of Schied et al. 2017, SVGF), estimated spatially from the image itself; DESIGN.md section 3.5. */
+enum { PT_DENOISE_FIXED = 0, PT_DENOISE_VARIANCE = 1 };
+/* Mode of the pt_denoise_render calls that follow — a GUI toggle's setter, like those MainWindow.cs:49-63 drives; the result is shown
+ * through ScreenEffect.cs:29-37; what is queued already keeps the mode it was issued under.  sigma_variance > 0: the width of the
+ * luminance stop in standard deviations, stored in both modes.  Defaults PT_DENOISE_FIXED, 6.  In PT_DENOISE_VARIANCE a stage in front
+ * of the passes estimates a variance per pixel (half the mean squared first difference of the tone-compressed luminance over the
+ * pixels of the same id in a 7x7 window), the passes filter it along with the colour, and iterations, sigma_plane and
+ * normal_log2_power of pt_denoise_set_params apply; sigma_color is not read, and nothing halves.  A non-finite sigma_variance or a mode
+ * other than the two: PT_E_BAD_ARGUMENT; sigma_variance <= 0: PT_E_OUT_OF_RANGE; the previous values stay in force then.  Scope as for
+ * pt_denoise_set_params. */
+PT_API int pt_denoise_set_mode(pt_handle h, int mode, float sigma_variance);
+/* The variance estimate of the last pt_denoise_render — the noise the filter saw in the image of MainWindow.cs:49-63 before it went to
+ * ScreenEffect.cs:29-37, one float per pixel (variance of the tone-compressed luminance; 0 on a miss), rows like the image: blocks;
+ * row_pitch_bytes >= width*4, 0 = tightly packed.  It doubles as a noise map: a host can stop showing the denoised image once the map
+ * is flat.  PT_E_BAD_ARGUMENT when nothing was rendered since the last (re)size / (re)tiling, when the last render ran in
+ * PT_DENOISE_FIXED, or with iterations = 0 (no estimate is made for a copy). */
+PT_API int pt_denoise_read_variance(pt_handle h, float *dst, size_t row_pitch_bytes);
 
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);

@@ -299,10 +299,13 @@ int free_first_hit(pt_handle h)
 int free_denoise(pt_handle h)
 {
     h->denoiseResult = -1;
-    if (!h->dGuides && !h->dDenoise[0] && !h->dDenoise[1]) return PT_OK;
+    h->denoiseVarianceValid = false;
+    if (!h->dGuides && !h->dDenoise[0] && !h->dDenoise[1] && !h->dVariance) return PT_OK;
     PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_denoise_render may still write them)
     if (h->dGuides) PT_HIP(h, hipFree(h->dGuides));
     h->dGuides = nullptr;
+    if (h->dVariance) PT_HIP(h, hipFree(h->dVariance));
+    h->dVariance = nullptr;
     for (float4 *&img : h->dDenoise) {
         if (img) PT_HIP(h, hipFree(img));
         img = nullptr;
@@ -560,6 +563,7 @@ PT_API int pt_destroy(pt_handle h)
     if (h->dFirstHit) (void)hipFree(h->dFirstHit);
     if (h->dPick) (void)hipFree(h->dPick);
     if (h->dGuides) (void)hipFree(h->dGuides);
+    if (h->dVariance) (void)hipFree(h->dVariance);
     if (h->dDenoise[0]) (void)hipFree(h->dDenoise[0]);
     if (h->dDenoise[1]) (void)hipFree(h->dDenoise[1]);
     if (h->dTimeline) (void)hipFree(h->dTimeline);
@@ -2227,24 +2231,60 @@ static int denoise_owner(pt_handle h)
     return PT_OK;
 }
 
-// stage < -1: everything; -1: the guides only; i >= 0: pass i only (pt_debug_denoise_stage, for timing)
+// stage kDenoiseAll: everything; -1: the guides only; kDenoiseStageV: stage V of the variance mode only; i >= 0: pass i only
+// (pt_debug_denoise_stage, for timing)
+constexpr int kDenoiseStageV = -2, kDenoiseAll = -3;
 static int denoise_run(pt_handle h, int guide_frame_index, int stage)
 {
     if (int rc = bind_device(h)) return rc;
     // (the preamble of pt_postprocess_device: pending frames are launched, an open frame-fed launch is closed, an abandoned hand-over is repaired)
     if (int rc = join_stripes(h)) return rc;
     const size_t pixels = h->tilePixels();
+    const bool variance = h->denoiseMode == PT_DENOISE_VARIANCE;
     if (!h->dGuides) PT_HIP(h, hipMalloc((void **)&h->dGuides, pixels * 2 * sizeof(float4)));
     for (float4 *&img : h->dDenoise)
         if (!img) PT_HIP(h, hipMalloc((void **)&img, pixels * sizeof(float4)));
-    if (stage < 0) {
+    if (variance && !h->dVariance) PT_HIP(h, hipMalloc((void **)&h->dVariance, pixels * sizeof(float)));
+    if (stage == kDenoiseAll || stage == -1) {
         pt::FrameArgs a;
         first_hit_args(h, a, guide_frame_index);
         PT_HIP(h, pt::launch_guides(a, h->dGuides, h->stream));
         if (stage == -1) return PT_OK;
     }
     const int n = h->denoiseIterations;
-    if (n == 0 && stage < 0) PT_HIP(h, pt::launch_denoise_copy(h->accum(), h->dDenoise[0], pixels, h->stream));
+    if (n == 0 && stage == kDenoiseAll) PT_HIP(h, pt::launch_denoise_copy(h->accum(), h->dDenoise[0], pixels, h->stream));
+    if (variance) {
+        if (n > 0 && (stage == kDenoiseAll || stage == kDenoiseStageV)) {
+            pt::VarianceArgs v;
+            v.colIn = h->accum();
+            v.guides = h->dGuides;
+            v.var = h->dVariance;
+            v.width = h->width;
+            v.height = h->rows;
+            PT_HIP(h, pt::launch_variance(v, h->stream));
+        }
+        for (int i = 0; i < n && stage != kDenoiseStageV; i++) {
+            if (stage >= 0 && i != stage) continue;
+            pt::AtrousVarArgs t;
+            t.colIn = i == 0 ? h->accum() : h->dDenoise[(i - 1) & 1];
+            t.varIn = i == 0 ? h->dVariance : nullptr;
+            t.guides = h->dGuides;
+            t.colOut = h->dDenoise[i & 1];
+            t.width = h->width;
+            t.height = h->rows;
+            t.step = 1 << i;
+            t.k2 = h->denoiseSigmaVariance * h->denoiseSigmaVariance;
+            t.sigmaPlane = h->denoiseSigmaPlane;
+            t.normalPower = h->denoiseNormalPower;
+            t.last = i == n - 1;
+            PT_HIP(h, pt::launch_atrous_var(t, h->stream));
+        }
+        if (stage == kDenoiseAll) {
+            h->denoiseResult = n == 0 ? 0 : (n - 1) & 1;
+            h->denoiseVarianceValid = n > 0;
+        }
+        return PT_OK;
+    }
     for (int i = 0; i < n; i++) {
         if (stage >= 0 && i != stage) continue;
         pt::AtrousArgs t;
@@ -2259,7 +2299,10 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
         t.normalPower = h->denoiseNormalPower;
         PT_HIP(h, pt::launch_atrous(t, h->stream));
     }
-    if (stage < 0) h->denoiseResult = n == 0 ? 0 : (n - 1) & 1;
+    if (stage == kDenoiseAll) {
+        h->denoiseResult = n == 0 ? 0 : (n - 1) & 1;
+        h->denoiseVarianceValid = false;
+    }
     return PT_OK;
 }
 
@@ -2277,12 +2320,24 @@ PT_API int pt_denoise_set_params(pt_handle h, int iterations, float sigma_color,
     return PT_OK;
 }
 
+PT_API int pt_denoise_set_mode(pt_handle h, int mode, float sigma_variance)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    if (mode != PT_DENOISE_FIXED && mode != PT_DENOISE_VARIANCE) return fail(h, PT_E_BAD_ARGUMENT, "mode must be PT_DENOISE_FIXED or PT_DENOISE_VARIANCE");
+    if (!std::isfinite(sigma_variance)) return fail(h, PT_E_BAD_ARGUMENT, "sigma_variance must be finite");
+    if (!(sigma_variance > 0.0f)) return fail(h, PT_E_OUT_OF_RANGE, "sigma_variance > 0");
+    h->denoiseMode = mode; // (read by the next pt_denoise_render; what is queued already took its values)
+    h->denoiseSigmaVariance = sigma_variance;
+    return PT_OK;
+}
+
 PT_API int pt_denoise_render(pt_handle h, int guide_frame_index)
 {
     PT_CHECK_HANDLE(h);
     if (guide_frame_index < 0) return fail(h, PT_E_BAD_ARGUMENT, "guide_frame_index must be >= 0");
     if (int rc = denoise_owner(h)) return rc;
-    return denoise_run(h, guide_frame_index, -2);
+    return denoise_run(h, guide_frame_index, kDenoiseAll);
 }
 
 static int denoise_rendered(pt_handle h)
@@ -2317,6 +2372,15 @@ PT_API int pt_denoise_read_guides(pt_handle h, void *dst, size_t row_pitch_bytes
     return denoise_copy_out(h, dst, row_pitch_bytes, h->dGuides, 32);
 }
 
+PT_API int pt_denoise_read_variance(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    if (!h->denoiseVarianceValid)
+        return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render made no variance estimate (PT_DENOISE_FIXED, or iterations = 0)");
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->dVariance, 4);
+}
+
 PT_API int pt_denoise_device_ptr(pt_handle h, void **out, size_t *bytes)
 {
     PT_CHECK_HANDLE(h);
@@ -2339,11 +2403,14 @@ PT_API int pt_denoise_present_rgba8(pt_handle h, uint8_t *dst, size_t row_pitch_
 }
 
 // Timing aid (not declared in the public header): one stage of pt_denoise_render on its own — stage -1 = the guide kernel, i >= 0 = pass i
-// between the buffers a full render uses (a pt_denoise_render must have run; the result it left is overwritten with a partial one).
+// of the mode in force, -2 = stage V (the variance estimate; PT_DENOISE_VARIANCE only) — between the buffers a full render uses (a
+// pt_denoise_render must have run; the result it left is overwritten with a partial one).
 extern "C" __attribute__((visibility("default"))) int pt_debug_denoise_stage(pt_handle h, int guide_frame_index, int stage)
 {
     PT_CHECK_HANDLE(h);
-    if (guide_frame_index < 0 || stage < -1 || stage >= h->denoiseIterations) return fail(h, PT_E_BAD_ARGUMENT, "stage must be -1 .. iterations - 1");
+    if (stage == kDenoiseStageV && (h->denoiseMode != PT_DENOISE_VARIANCE || h->denoiseIterations == 0))
+        return fail(h, PT_E_BAD_ARGUMENT, "stage -2 needs PT_DENOISE_VARIANCE and iterations > 0");
+    if (guide_frame_index < 0 || stage < kDenoiseStageV || stage >= h->denoiseIterations) return fail(h, PT_E_BAD_ARGUMENT, "stage must be -2 .. iterations - 1");
     if (int rc = denoise_rendered(h)) return rc;
     return denoise_run(h, guide_frame_index, stage);
 }

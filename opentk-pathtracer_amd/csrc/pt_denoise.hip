@@ -186,4 +186,177 @@ hipError_t launch_denoise_copy(const float4 *in, float4 *out, size_t n, hipStrea
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------- variance-guided mode (PT_DENOISE_VARIANCE)
+// Stage V: V0(p) = half the mean squared first difference of u over the pixels of p's id in the 7x7 window around p — the
+// spatial variance estimate the luminance stop of the variance passes is scaled by.  16x16 tiles, one pixel per lane; (u, id bits) of the
+// tile and a halo of 3 towards left / bottom and 4 towards right / top (the +1 of Dx / Dy) staged into LDS: 23 x 23 cells of 8 bytes, u
+// divided out once per staged cell.  Cells outside the image hold an id no guide record has, so "outside" and "another id" are one
+// comparison.  A lane keeps two window rows of 8 cells in registers (64 ds_read_b64 per pixel); Dx and Dy are formed from them and added
+// under selects in the order of the definition (dy outer, dx inner, Dx before Dy).
+// R = 3, the window's radius: a template so that the kernel is emitted behind pt_atrous_kernel<S> and leaves that code as it was.
+constexpr int kVarOutsideId = (int)0x80000000;
+
+template <int R>
+__global__ __launch_bounds__(256) void pt_variance_kernel(const VarianceArgs a)
+{
+    static_assert(R == 3, "the definition's 7x7 window");
+    constexpr int LW = 23;
+    __shared__ float2 sU[LW * LW];
+    const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
+    const int x0 = blockIdx.x * 16, y0 = blockIdx.y * 16;
+    const int px = x0 + lx, py = y0 + ly;
+    for (int i = tid; i < LW * LW; i += 256) {
+        const int qx = x0 - 3 + i % LW, qy = y0 - 3 + i / LW;
+        float2 cell = make_float2(0.0f, __int_as_float(kVarOutsideId));
+        if (qx >= 0 && qx < a.width && qy >= 0 && qy < a.height) {
+            const size_t at = (size_t)qy * a.width + qx;
+            const float4 c = a.colIn[at];
+            cell = make_float2(dn_u(c.x, c.y, c.z), a.guides[2 * at].w);
+        }
+        sU[i] = cell;
+    }
+    __syncthreads();
+    if (px >= a.width || py >= a.height) return;
+    const int lc = (ly + 3) * LW + lx + 3;
+    const int idp = __float_as_int(sU[lc].y);
+    float v = 0.0f;
+    if (idp != -1) {
+        float n = 0.0f, s = 0.0f;
+        float2 cur[8], nxt[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) cur[k] = sU[lc - 3 * LW - 3 + k];
+#pragma unroll 1
+        for (int dy = -3; dy <= 3; dy++) { // (rolled: unrolled, the 98 validity masks are all formed first and spill the scalar registers)
+#pragma unroll
+            for (int k = 0; k < 8; k++) nxt[k] = sU[lc + (dy + 1) * LW - 3 + k];
+#pragma unroll
+            for (int k = 0; k < 7; k++) { // q = p + (k - 3, dy)
+                const bool visit = __float_as_int(cur[k].y) == idp;
+                const bool vx = visit && __float_as_int(cur[k + 1].y) == idp;
+                const bool vy = visit && __float_as_int(nxt[k].y) == idp;
+                const float ex = cur[k + 1].x - cur[k].x;
+                const float Dx = ex * ex;
+                n = vx ? n + 1.0f : n;
+                s = vx ? s + Dx : s;
+                const float ey = nxt[k].x - cur[k].x;
+                const float Dy = ey * ey;
+                n = vy ? n + 1.0f : n;
+                s = vy ? s + Dy : s;
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) cur[k] = nxt[k];
+        }
+        if (n > 0.0f) v = 0.5f * (s / n);
+    }
+    a.var[(size_t)py * a.width + px] = v;
+}
+
+hipError_t launch_variance(const VarianceArgs &a, hipStream_t stream)
+{
+    if (a.width < 1 || a.height < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_variance_kernel<3>, dim3((a.width + 15) / 16, (a.height + 15) / 16), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// One variance pass: pt_atrous_kernel<S> with the luminance stop scaled by the centre's variance, and the variance filtered along with the
+// colour (Q += w^2 var_q; output Q / W^2).  The variance of the input travels in colIn's alpha — on pass 0 in a.varIn, the estimate of
+// stage V, since the accumulation image's alpha carries frame tags — and that of the output in colOut's alpha (a.last: alpha = 1).
+// S = 1, 2: the LDS layout of pt_atrous_kernel<S> plus one float per staged pixel for the variance: 52 bytes per pixel, 29,952 bytes at
+// S = 2.  S = 0: direct taps, the variance read with the colour.
+template <int S>
+__global__ __launch_bounds__(256) void pt_atrous_var_kernel(const AtrousVarArgs a)
+{
+    constexpr int TX = S ? 16 : 64, TY = S ? 16 : 4, HALO = 2 * S, LW = TX + 2 * HALO, LH = TY + 2 * HALO;
+    __shared__ float4 sG0[S ? LW * LH : 1], sG1[S ? LW * LH : 1], sC[S ? LW * LH : 1];
+    __shared__ float sV[S ? LW * LH : 1];
+    const int tid = threadIdx.x, lx = tid % TX, ly = tid / TX;
+    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+    const int px = x0 + lx, py = y0 + ly;
+    const int step = S ? S : a.step;
+    if constexpr (S != 0) {
+        for (int i = tid; i < LW * LH; i += 256) {
+            const int qx = x0 - HALO + i % LW, qy = y0 - HALO + i / LW;
+            if (qx >= 0 && qx < a.width && qy >= 0 && qy < a.height) { // (cells outside the image are never read: their taps are skipped)
+                const size_t at = (size_t)qy * a.width + qx;
+                float4 c = a.colIn[at];
+                sV[i] = a.varIn ? a.varIn[at] : c.w;
+                c.w = dn_u(c.x, c.y, c.z);
+                sG0[i] = a.guides[2 * at];
+                sG1[i] = a.guides[2 * at + 1];
+                sC[i] = c;
+            }
+        }
+        __syncthreads();
+    }
+    if (px >= a.width || py >= a.height) return;
+    const size_t center = (size_t)py * a.width + px;
+    const int lc = (ly + HALO) * LW + lx + HALO;
+    const float4 g0p = S ? sG0[lc] : a.guides[2 * center];
+    const float4 g1p = S ? sG1[lc] : a.guides[2 * center + 1];
+    float4 cp = S ? sC[lc] : a.colIn[center];
+    const float varp = S ? sV[lc] : (a.varIn ? a.varIn[center] : cp.w);
+    const int idp = __float_as_int(g0p.w);
+    float4 out = make_float4(cp.x, cp.y, cp.z, varp);
+    if (idp != -1) {
+        const float up = S ? cp.w : dn_u(cp.x, cp.y, cp.z);
+        const float planeDen = a.sigmaPlane * g1p.w;
+        const float invp = 1.0f / (a.k2 * varp + 1e-8f);
+        float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, Q = 0.0f;
+#pragma unroll
+        for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; dx++) {
+                const float kx = dx == 0 ? 0.375f : (dx == 1 || dx == -1 ? 0.25f : 0.0625f);
+                const float ky = dy == 0 ? 0.375f : (dy == 1 || dy == -1 ? 0.25f : 0.0625f);
+                const float hk = kx * ky; // (exact)
+                const int qx = px + step * dx, qy = py + step * dy;
+                if (qx < 0 || qx >= a.width || qy < 0 || qy >= a.height) continue;
+                const size_t at = (size_t)qy * a.width + qx;
+                const int lq = lc + dy * S * LW + dx * S;
+                const float4 g0q = S ? sG0[lq] : a.guides[2 * at];
+                if (__float_as_int(g0q.w) != idp) continue;
+                const float4 g1q = S ? sG1[lq] : a.guides[2 * at + 1];
+                const float4 cq = S ? sC[lq] : a.colIn[at];
+                const float varq = S ? sV[lq] : (a.varIn ? a.varIn[at] : cq.w);
+                const float d = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
+                float wn = d > 0.0f ? d : 0.0f;
+                for (int k = 0; k < a.normalPower; k++) wn = wn * wn;
+                const float ex = g0q.x - g0p.x, ey = g0q.y - g0p.y, ez = g0q.z - g0p.z;
+                const float e = (g1p.x * ex + g1p.y * ey) + g1p.z * ez;
+                const float r = e / planeDen;
+                const float z = 1.0f - r * r;
+                const float wz = z > 0.0f ? z : 0.0f;
+                const float uq = S ? cq.w : dn_u(cq.x, cq.y, cq.z);
+                const float du = uq - up;
+                const float a2 = (du * du) * invp;
+                const float c1 = 1.0f - a2;
+                const float c2 = c1 > 0.0f ? c1 : 0.0f;
+                const float wc = c2 * c2;
+                const float w = ((hk * wn) * wz) * wc;
+                W = W + w;
+                Sr = Sr + w * cq.x;
+                Sg = Sg + w * cq.y;
+                Sb = Sb + w * cq.z;
+                Q = Q + (w * w) * varq;
+            }
+        }
+        if (W > 0.0f) out = make_float4(Sr / W, Sg / W, Sb / W, Q / (W * W));
+    }
+    if (a.last) out.w = 1.0f;
+    a.colOut[center] = out;
+}
+
+hipError_t launch_atrous_var(const AtrousVarArgs &a, hipStream_t stream)
+{
+    if (a.width < 1 || a.height < 1 || a.step < 1) return hipErrorInvalidValue;
+    if (a.step <= 2) {
+        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+        if (a.step == 1) hipLaunchKernelGGL(pt_atrous_var_kernel<1>, grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(pt_atrous_var_kernel<2>, grid, dim3(256), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL(pt_atrous_var_kernel<0>, dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
 } // namespace pt

@@ -241,6 +241,29 @@ struct AtrousArgs {
 };
 hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream);
 hipError_t launch_denoise_copy(const float4 *in, float4 *out, size_t pixels, hipStream_t stream); // out = (in.rgb, 1)
+// the variance-guided mode (PT_DENOISE_VARIANCE).  Stage V: var[pixel] = the spatial variance estimate V0 of u(colIn.rgb) within the pixel's id
+struct VarianceArgs {
+    const float4 *colIn;  // alpha is not read
+    const float4 *guides;
+    float *var;           // width x height floats, compact rows
+    int width, height;
+};
+hipError_t launch_variance(const VarianceArgs &a, hipStream_t stream);
+// one variance pass colIn -> colOut: the variance of the input is varIn (pass 0: stage V's buffer) or, where varIn is null, colIn's alpha;
+// that of the output is colOut's alpha, or alpha = 1 on the last pass
+struct AtrousVarArgs {
+    const float4 *colIn;
+    const float *varIn;
+    const float4 *guides;
+    float4 *colOut;
+    int width, height;
+    int step;         // 2^i for pass i
+    float k2;         // sigma_variance * sigma_variance, computed by the host in binary32
+    float sigmaPlane;
+    int normalPower;  // the normal weight is squared this many times
+    int last;         // the last pass writes alpha 1
+};
+hipError_t launch_atrous_var(const AtrousVarArgs &a, hipStream_t stream);
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 // the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);

@@ -176,6 +176,12 @@ struct pt_renderer {
     int denoiseResult = -1;
     int denoiseIterations = 5, denoiseNormalPower = 5; // pt_denoise_set_params
     float denoiseSigmaColor = 0.5f, denoiseSigmaPlane = 0.02f;
+    // Variance-guided mode (pt_denoise_set_mode): dVariance = stage V's estimate V0, rows x width floats, allocated by the first
+    // pt_denoise_render in that mode and freed with the buffers above; denoiseVarianceValid: the last pt_denoise_render made one.
+    int denoiseMode = 0; // PT_DENOISE_FIXED
+    float denoiseSigmaVariance = 6.0f;
+    float *dVariance = nullptr;
+    bool denoiseVarianceValid = false;
 
     // hand-over audit (only allocated by the -DPT_AUDIT build, see pt_debug_hooks.hpp): side word per accumulation pixel + violation log
     unsigned long long *dAudit = nullptr;

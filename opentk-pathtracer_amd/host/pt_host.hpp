@@ -350,6 +350,16 @@ public:
         Check(pt_denoise_read_guides(h_, rec.data(), 0), h_);
         return rec;
     }
+    // PT_DENOISE_FIXED (sigmaColor, halved every pass) or PT_DENOISE_VARIANCE (the luminance stop is sigmaVariance standard deviations of
+    // each pixel's own noise, estimated from the image) for the Denoise() calls that follow
+    void SetDenoiseMode(int mode, float sigmaVariance = 6.0f) { Check(pt_denoise_set_mode(h_, mode, sigmaVariance), h_); }
+    // the variance estimate of the last Denoise() in PT_DENOISE_VARIANCE: one float per pixel, row 0 = bottom — a noise map
+    std::vector<float> DenoiseVariance() const
+    {
+        std::vector<float> var((size_t)width_ * height_);
+        Check(pt_denoise_read_variance(h_, var.data(), 0), h_);
+        return var;
+    }
     // ScreenEffect.Render (src/Render/ScreenEffect.cs:29-37) of the last Denoise() instead of `Result`
     std::vector<uint8_t> PresentDenoised() const
     {

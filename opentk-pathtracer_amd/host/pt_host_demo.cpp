@@ -11,9 +11,10 @@
 //   pt_host_demo pick <W> <H> <x> <y> [frame]
 //                      MainWindow.RayTrace for the pixel under the cursor (Gui.cs:223-233 -> MainWindow.cs:302-318), answered by the
 //                      integrator's own ray: prints the object and its distance, and focuses the thin lens on it (FocalLength = distance)
-//   pt_host_demo denoise <W> <H> <frames> <out.rgba8> [iterations]
+//   pt_host_demo denoise <W> <H> <frames> <out.rgba8> [iterations] [sigmaVariance]
 //                      the first frames after a ResetRenderer() (MainWindow.cs:58-63), shown through the preview denoiser: N x Render(),
-//                      then Denoise() + PresentDenoised() in place of ScreenEffect.Render(PathTracer.Result) (MainWindow.cs:49-56)
+//                      then Denoise() + PresentDenoised() in place of ScreenEffect.Render(PathTracer.Result) (MainWindow.cs:49-56);
+//                      sigmaVariance > 0: the variance-guided mode, and the mean of its noise map is printed
 //   pt_host_demo dump-scene <out.bin>            (no GPU needed: the 26,624-byte GameObjectsUBO image)
 //   pt_host_demo dump-camera <W> <H> <out.bin>   (no GPU needed: the 144-byte BasicDataUBO image)
 #include <cstdio>
@@ -95,6 +96,8 @@ int main(int argc, char **argv)
             LoadScene(pathTracer);
             UploadCamera(pathTracer, camera, W, H);
             if (argc > 6) pathTracer.SetDenoise(std::atoi(argv[6]));
+            const bool varianceGuided = argc > 7 && std::atof(argv[7]) > 0.0;
+            if (varianceGuided) pathTracer.SetDenoiseMode(PT_DENOISE_VARIANCE, (float)std::atof(argv[7]));
             std::vector<uint8_t> shown;
             for (int i = 0; i < frames; i++) {
                 pathTracer.Render();                  // OnRenderFrame, MainWindow.cs:49
@@ -102,6 +105,12 @@ int main(int argc, char **argv)
                 shown = pathTracer.PresentDenoised(); // :51 — ScreenEffect.Render of the filtered image; `Result` keeps accumulating untouched
             }
             write_file(argv[5], shown.data(), shown.size());
+            if (varianceGuided && frames > 0 && std::atoi(argv[6]) > 0) { // the noise map: a host stops showing the denoised image once it is flat
+                const std::vector<float> var = pathTracer.DenoiseVariance();
+                double sum = 0.0;
+                for (float v : var) sum += v;
+                std::printf("mean variance estimate of the last frame %.3g\n", sum / (double)var.size());
+            }
             std::printf("showed %dx%d denoised, %d samples/pixel\n", W, H, pathTracer.Samples());
             return 0;
         }
@@ -157,7 +166,7 @@ int main(int argc, char **argv)
             std::printf("resumed at frame %d, now %d samples/pixel\n", restored, second.Samples());
             return 0;
         }
-        std::fprintf(stderr, "usage: pt_host_demo render W H frames out.f32 [rayDepth] [atmoSize] | pick W H x y [frame] | denoise W H frames out.rgba8 [iterations] | frame-loop W H frames out.rgba8 devices | resume W H framesA framesB out.f32 ckpt shot.ppm | "
+        std::fprintf(stderr, "usage: pt_host_demo render W H frames out.f32 [rayDepth] [atmoSize] | pick W H x y [frame] | denoise W H frames out.rgba8 [iterations] [sigmaVariance] | frame-loop W H frames out.rgba8 devices | resume W H framesA framesB out.f32 ckpt shot.ppm | "
                              "dump-scene out.bin | dump-camera W H out.bin\n");
         return 1;
     } catch (const std::exception &e) {

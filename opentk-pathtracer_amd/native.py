@@ -31,6 +31,7 @@ PT_E_BAD_HANDLE, PT_E_BAD_ARGUMENT, PT_E_OUT_OF_RANGE, PT_E_NO_ENVIRONMENT, PT_E
 PT_ENV_RGBA32F, PT_ENV_SRGB8_A8 = 0, 1
 PT_MAX_SPHERES, PT_MAX_CUBOIDS = 256, 64  # first-hit ids: sphere i = i, cuboid j = PT_MAX_SPHERES + j, miss = -1
 PT_ARITH_CONTRACT, PT_ARITH_REFERENCE = 0, 1  # pt_set_arithmetic, pt_atmosphere_set_arithmetic, pt_present_set_arithmetic
+PT_DENOISE_FIXED, PT_DENOISE_VARIANCE = 0, 1  # pt_denoise_set_mode
 
 
 class NativeError(RuntimeError):
@@ -221,6 +222,8 @@ def load() -> C.CDLL:
         "pt_denoise_read_guides": [vp, vp, C.c_size_t],
         "pt_denoise_device_ptr": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
         "pt_denoise_present_rgba8": [vp, C.POINTER(C.c_uint8), C.c_size_t],
+        "pt_denoise_set_mode": [vp, C.c_int, C.c_float],
+        "pt_denoise_read_variance": [vp, fp, C.c_size_t],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -280,7 +283,7 @@ def debug_handover_stats(handle) -> dict:
 
 def debug_denoise_stage(handle, frame: int, stage: int) -> None:
     """One stage of pt_denoise_render on its own, for timing (pt_debug_denoise_stage — exported, not in the public header): stage -1 = the
-    guide kernel, i >= 0 = pass i.  A pt_denoise_render must have run; the result it left is overwritten with a partial one."""
+    guide kernel, i >= 0 = pass i of the mode in force, -2 = the variance estimate (PT_DENOISE_VARIANCE only).  A pt_denoise_render must have run; the result it left is overwritten with a partial one."""
     L = load()
     L.pt_debug_denoise_stage.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pt_debug_denoise_stage.restype = C.c_int

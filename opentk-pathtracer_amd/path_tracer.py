@@ -315,6 +315,17 @@ class PathTracer:
         check(self._lib.pt_denoise_read_guides(self._h, out.ctypes.data_as(C.c_void_p), 0), self._h)
         return out
 
+    def SetDenoiseMode(self, mode: int, sigma_variance: float = 6.0) -> None:
+        """pt_denoise_set_mode: PT_DENOISE_FIXED (sigma_color, halved every pass) or PT_DENOISE_VARIANCE (the luminance stop is
+        sigma_variance standard deviations of each pixel's own noise, estimated from the image) for the Denoise calls that follow."""
+        check(self._lib.pt_denoise_set_mode(self._h, mode, sigma_variance), self._h)
+
+    def DenoiseVariance(self) -> np.ndarray:
+        """pt_denoise_read_variance: the variance estimate V0 of the last Denoise in PT_DENOISE_VARIANCE as (rows, Width) float32."""
+        out = np.empty((self.rows, self.Width), dtype=np.float32)
+        check(self._lib.pt_denoise_read_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
+        return out
+
     def PresentDenoised(self) -> np.ndarray:
         """pt_denoise_present_rgba8: the result of the last Denoise through the tone map Present applies, as (rows, Width, 4) uint8."""
         out = np.empty((self.rows, self.Width, 4), dtype=np.uint8)
