@@ -392,6 +392,39 @@ PT_API int pt_denoise_set_mode(pt_handle h, int mode, float sigma_variance);
  * PT_DENOISE_FIXED, or with iterations = 0 (no estimate is made for a copy). */
 PT_API int pt_denoise_read_variance(pt_handle h, float *dst, size_t row_pitch_bytes);
 
+/* The temporal stage (the temporal half of SVGF, Schied et al. 2017): in front of the passes, the result of the
+ * previous view is reprojected through the guide records and blended with the image by sample counts, so that the first frames after
+ * the reset a camera move causes show tens of samples per pixel instead of one.  The handle keeps two SETS — an integrated image I
+ * (RGBA32F: rgb, alpha = the per-pixel sample count), its guide records and its camera — the CURRENT one and the HISTORY, and counts
+ * RESET EPOCHS: pt_reset, pt_write_result, pt_set_size, pt_set_tile and pt_set_interleaved_tile each begin a new one.  A temporal
+ * pt_denoise_render whose current set is of an earlier epoch first makes it the history (a pointer swap); then it renders the guides,
+ * integrates I(p) = ((n C + m' Hc) / (n + m'), n + m') — C the image, n = frame index * spp, Hc and m the history's colour and count
+ * found at p's reprojected position among the pixels of p's id, m' = min(m, max_history) — or I(p) = (C, n) where nothing is found,
+ * and filters I in the mode in force in place of the image.  Within one epoch repeated calls reuse the same history and integrate
+ * afresh: nothing is counted twice.  n = 0 (a reset with no frame rendered yet) shows the old view warped to the new camera.  With
+ * the stage off (the default) pt_denoise_render neither reads nor writes either set and its results are bit for bit what they were. */
+
+/* Switch of the pt_denoise_render calls that follow — a GUI toggle's setter, like those MainWindow.cs:49-63 drives; the result is shown
+ * through ScreenEffect.cs:29-37; what is queued already keeps the values it was issued under.  enable: 0 or 1, anything else
+ * PT_E_BAD_ARGUMENT; max_history 1..65535 (the cap of the count a history pixel brings along: the smaller, the faster stale lighting
+ * fades), outside that PT_E_OUT_OF_RANGE; the previous values stay in force then.  Defaults 0, 32.  Scope as for pt_denoise_set_params. */
+PT_API int pt_denoise_set_temporal(pt_handle h, int enable, int max_history);
+/* Forgets both sets: the next temporal pt_denoise_render finds no history (I = (C, n)) — what a host calls after a scene, material or
+ * environment edit (the GUI edits beside the camera moves of MainWindow.cs:49-63, shown through ScreenEffect.cs:29-37), which changes
+ * the colours the history holds, not only where they are seen from.  Frees nothing.  Scope as for pt_denoise_set_params. */
+PT_API int pt_denoise_history_clear(pt_handle h);
+/* The integrated image I of the last pt_denoise_render made with the temporal stage on — the input of the passes in place of the image
+ * of MainWindow.cs:49-63, before the filter and ScreenEffect.cs:29-37 — RGBA32F, alpha = the per-pixel sample count (it doubles as a
+ * history-length map), rows like the image; row_pitch_bytes >= width*16, 0 = tightly packed.  PT_E_BAD_ARGUMENT when the last render
+ * ran with the stage off, or when nothing was rendered since the last (re)size / (re)tiling. */
+PT_API int pt_denoise_read_integrated(pt_handle h, float *dst, size_t row_pitch_bytes);
+/* The history set the last temporal pt_denoise_render used (the previous view of MainWindow.cs:49-63, as it went to
+ * ScreenEffect.cs:29-37's input): image = its I (width*height RGBA32F), guides = its 32-byte guide records (as pt_denoise_read_guides),
+ * both tightly packed; out_B = the inverse of its camera's ray matrix, row-major, out_O = its ray origin (the InvView translation):
+ * out_B (P - out_O) = lambda (ndc x, ndc y, 1) for a point P seen by that camera.  Every pointer may be NULL.  PT_E_BAD_ARGUMENT when
+ * that render had no history (or none was made since the last (re)size / (re)tiling / pt_denoise_history_clear). */
+PT_API int pt_denoise_read_history(pt_handle h, float *image, void *guides, float out_B[9], float out_O[3]);
+
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);
 PT_API int pt_device_count(void);

@@ -300,7 +300,11 @@ int free_denoise(pt_handle h)
 {
     h->denoiseResult = -1;
     h->denoiseVarianceValid = false;
-    if (!h->dGuides && !h->dDenoise[0] && !h->dDenoise[1] && !h->dVariance) return PT_OK;
+    h->denoiseIntegratedValid = h->denoiseHistoryUsed = false;
+    for (pt_renderer::DenoiseSet &set : h->denoiseSet) set.valid = false;
+    if (!h->dGuides && !h->dDenoise[0] && !h->dDenoise[1] && !h->dVariance && !h->denoiseSet[0].image && !h->denoiseSet[0].guides &&
+        !h->denoiseSet[1].image && !h->denoiseSet[1].guides)
+        return PT_OK;
     PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_denoise_render may still write them)
     if (h->dGuides) PT_HIP(h, hipFree(h->dGuides));
     h->dGuides = nullptr;
@@ -309,6 +313,12 @@ int free_denoise(pt_handle h)
     for (float4 *&img : h->dDenoise) {
         if (img) PT_HIP(h, hipFree(img));
         img = nullptr;
+    }
+    for (pt_renderer::DenoiseSet &set : h->denoiseSet) {
+        if (set.image) PT_HIP(h, hipFree(set.image));
+        set.image = nullptr;
+        if (set.guides) PT_HIP(h, hipFree(set.guides));
+        set.guides = nullptr;
     }
     return PT_OK;
 }
@@ -566,6 +576,10 @@ PT_API int pt_destroy(pt_handle h)
     if (h->dVariance) (void)hipFree(h->dVariance);
     if (h->dDenoise[0]) (void)hipFree(h->dDenoise[0]);
     if (h->dDenoise[1]) (void)hipFree(h->dDenoise[1]);
+    for (pt_renderer::DenoiseSet &set : h->denoiseSet) {
+        if (set.image) (void)hipFree(set.image);
+        if (set.guides) (void)hipFree(set.guides);
+    }
     if (h->dTimeline) (void)hipFree(h->dTimeline);
     if (h->evBegin) (void)hipEventDestroy(h->evBegin);
     if (h->evEnd) (void)hipEventDestroy(h->evEnd);
@@ -587,6 +601,7 @@ PT_API int pt_set_size(pt_handle h, int width, int height)
     if (int rc = join_stripes(h)) return rc; // (the launches so far — and their hand-over repair passes — belong to the buffers as they are)
     if (int rc = ptimpl::free_first_hit(h)) return rc;
     if (int rc = ptimpl::free_denoise(h)) return rc;
+    h->resetEpoch++;
     h->width = width;
     h->height = height;
     h->y0 = 0;
@@ -609,6 +624,7 @@ PT_API int pt_set_tile(pt_handle h, int y0, int rows)
     if (int rc = join_stripes(h)) return rc; // (see pt_set_size)
     if (int rc = ptimpl::free_first_hit(h)) return rc;
     if (int rc = ptimpl::free_denoise(h)) return rc;
+    h->resetEpoch++;
     h->y0 = y0;
     h->rows = rows;
     h->bandRows = 0;
@@ -637,6 +653,7 @@ PT_API int pt_set_interleaved_tile(pt_handle h, int rank, int world, int band_ro
     if (int rc = join_stripes(h)) return rc; // (see pt_set_size)
     if (int rc = ptimpl::free_first_hit(h)) return rc;
     if (int rc = ptimpl::free_denoise(h)) return rc;
+    h->resetEpoch++;
     h->y0 = 0;
     h->rows = (int)rows;
     h->bandRows = band_rows;
@@ -670,6 +687,7 @@ PT_API int pt_reset(pt_handle h)
     if (int rc = bind_device(h)) return rc;
     if (int rc = ptimpl::fix_alpha(h)) return rc;
     h->frame = 0; // PathTracer.cs:139 — frame 0 weights the old contents by 0, so no clear is needed
+    h->resetEpoch++; // (the temporal stage of the denoiser: what it integrated so far belongs to the view that ends here)
     return audit_forget(h);
 }
 
@@ -1680,6 +1698,7 @@ PT_API int pt_write_result(pt_handle h, const float *src, size_t row_pitch_bytes
     if (int rc = audit_forget(h)) return rc;
     PT_HIP(h, hipStreamSynchronize(h->stream));
     h->frame = frame_index;
+    h->resetEpoch++;
     return PT_OK;
 }
 
@@ -2231,9 +2250,40 @@ static int denoise_owner(pt_handle h)
     return PT_OK;
 }
 
-// stage kDenoiseAll: everything; -1: the guides only; kDenoiseStageV: stage V of the variance mode only; i >= 0: pass i only
-// (pt_debug_denoise_stage, for timing)
-constexpr int kDenoiseStageV = -2, kDenoiseAll = -3;
+// The camera of a set: the ray generator is linear in the NDC point, wd = A (ndcx, ndcy, 1) with A = [a b c] formed
+// from the blob's InvProjection m and InvView v (compute.glsl:352-357 as primary_ray_cam evaluates it); B = A^-1, formed and inverted in
+// double and rounded to binary32 once, O = InvView's translation.  false: A is singular or B not finite.
+static bool denoise_set_camera(const unsigned char *basic, float B[9], float O[3])
+{
+    float m[16], v[16];
+    std::memcpy(m, basic, 64);
+    std::memcpy(v, basic + 64, 64);
+    double A[3][3];
+    for (int r = 0; r < 3; r++) {
+        A[r][0] = (double)v[r] * m[0] + (double)v[4 + r] * m[1];
+        A[r][1] = (double)v[r] * m[4] + (double)v[4 + r] * m[5];
+        A[r][2] = -((double)v[r] * m[8] + (double)v[4 + r] * m[9]) - (double)v[8 + r];
+        O[r] = v[12 + r];
+    }
+    double C[3][3]; // cofactors: A^-1 = C^T / det
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            C[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1];
+        }
+    const double det = A[0][0] * C[0][0] + A[0][1] * C[0][1] + A[0][2] * C[0][2];
+    bool ok = std::isfinite(det) && det != 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            B[3 * i + j] = (float)(C[j][i] / det);
+            ok = ok && std::isfinite(B[3 * i + j]);
+        }
+    return ok;
+}
+
+// stage kDenoiseAll: everything; -1: the guides only; kDenoiseStageV: stage V of the variance mode only; kDenoiseStageT: the temporal
+// kernel only; i >= 0: pass i only (pt_debug_denoise_stage, for timing)
+constexpr int kDenoiseStageV = -2, kDenoiseAll = -3, kDenoiseStageT = -4;
 static int denoise_run(pt_handle h, int guide_frame_index, int stage)
 {
     if (int rc = bind_device(h)) return rc;
@@ -2241,23 +2291,61 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
     if (int rc = join_stripes(h)) return rc;
     const size_t pixels = h->tilePixels();
     const bool variance = h->denoiseMode == PT_DENOISE_VARIANCE;
-    if (!h->dGuides) PT_HIP(h, hipMalloc((void **)&h->dGuides, pixels * 2 * sizeof(float4)));
+    const bool temporal = h->denoiseTemporal != 0;
+    if (!temporal && !h->dGuides) PT_HIP(h, hipMalloc((void **)&h->dGuides, pixels * 2 * sizeof(float4)));
     for (float4 *&img : h->dDenoise)
         if (!img) PT_HIP(h, hipMalloc((void **)&img, pixels * sizeof(float4)));
     if (variance && !h->dVariance) PT_HIP(h, hipMalloc((void **)&h->dVariance, pixels * sizeof(float)));
+    if (temporal) {
+        for (pt_renderer::DenoiseSet &set : h->denoiseSet) {
+            if (!set.image) PT_HIP(h, hipMalloc((void **)&set.image, pixels * sizeof(float4)));
+            if (!set.guides) PT_HIP(h, hipMalloc((void **)&set.guides, pixels * 2 * sizeof(float4)));
+        }
+        // a current set of an earlier reset epoch becomes the history: a pointer swap (a timing stage works between the sets as they are)
+        if (stage == kDenoiseAll && h->denoiseSet[h->denoiseCurrent].valid && h->denoiseSet[h->denoiseCurrent].epoch != h->resetEpoch) {
+            h->denoiseCurrent ^= 1;
+            h->denoiseSet[h->denoiseCurrent].valid = false; // (until this render has made it)
+        }
+    }
+    pt_renderer::DenoiseSet &cur = h->denoiseSet[h->denoiseCurrent];
+    const pt_renderer::DenoiseSet &hist = h->denoiseSet[h->denoiseCurrent ^ 1];
+    float4 *const guides = temporal ? cur.guides : h->dGuides; // the guides of this render ...
+    const float4 *const first = temporal ? cur.image : h->accum(); // ... and C_0, the input of stage V and of pass 0
     if (stage == kDenoiseAll || stage == -1) {
         pt::FrameArgs a;
         first_hit_args(h, a, guide_frame_index);
-        PT_HIP(h, pt::launch_guides(a, h->dGuides, h->stream));
+        PT_HIP(h, pt::launch_guides(a, guides, h->stream));
         if (stage == -1) return PT_OK;
     }
+    if (temporal && (stage == kDenoiseAll || stage == kDenoiseStageT)) {
+        pt::TemporalArgs t;
+        t.colIn = h->accum();
+        t.guides = guides;
+        t.histImage = hist.valid ? hist.image : nullptr;
+        t.histGuides = hist.guides;
+        t.out = cur.image;
+        t.width = h->width;
+        t.height = h->rows;
+        t.n = (float)((long long)h->frame * h->spp);
+        t.maxHistory = (float)h->denoiseMaxHistory;
+        std::memcpy(t.B, hist.B, sizeof t.B);
+        std::memcpy(t.O, hist.O, sizeof t.O);
+        t.sigmaPlane = h->denoiseSigmaPlane;
+        t.normalPower = h->denoiseNormalPower;
+        PT_HIP(h, pt::launch_temporal(t, h->stream));
+        if (stage == kDenoiseStageT) return PT_OK;
+        cur.valid = denoise_set_camera(h->basic, cur.B, cur.O);
+        cur.epoch = h->resetEpoch;
+        h->denoiseHistoryUsed = hist.valid;
+    }
+    if (stage == kDenoiseAll) h->denoiseIntegratedValid = temporal;
     const int n = h->denoiseIterations;
-    if (n == 0 && stage == kDenoiseAll) PT_HIP(h, pt::launch_denoise_copy(h->accum(), h->dDenoise[0], pixels, h->stream));
+    if (n == 0 && stage == kDenoiseAll) PT_HIP(h, pt::launch_denoise_copy(first, h->dDenoise[0], pixels, h->stream));
     if (variance) {
         if (n > 0 && (stage == kDenoiseAll || stage == kDenoiseStageV)) {
             pt::VarianceArgs v;
-            v.colIn = h->accum();
-            v.guides = h->dGuides;
+            v.colIn = first;
+            v.guides = guides;
             v.var = h->dVariance;
             v.width = h->width;
             v.height = h->rows;
@@ -2266,9 +2354,9 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
         for (int i = 0; i < n && stage != kDenoiseStageV; i++) {
             if (stage >= 0 && i != stage) continue;
             pt::AtrousVarArgs t;
-            t.colIn = i == 0 ? h->accum() : h->dDenoise[(i - 1) & 1];
+            t.colIn = i == 0 ? first : h->dDenoise[(i - 1) & 1];
             t.varIn = i == 0 ? h->dVariance : nullptr;
-            t.guides = h->dGuides;
+            t.guides = guides;
             t.colOut = h->dDenoise[i & 1];
             t.width = h->width;
             t.height = h->rows;
@@ -2288,8 +2376,8 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
     for (int i = 0; i < n; i++) {
         if (stage >= 0 && i != stage) continue;
         pt::AtrousArgs t;
-        t.colIn = i == 0 ? h->accum() : h->dDenoise[(i - 1) & 1];
-        t.guides = h->dGuides;
+        t.colIn = i == 0 ? first : h->dDenoise[(i - 1) & 1];
+        t.guides = guides;
         t.colOut = h->dDenoise[i & 1];
         t.width = h->width;
         t.height = h->rows;
@@ -2369,7 +2457,7 @@ PT_API int pt_denoise_read_guides(pt_handle h, void *dst, size_t row_pitch_bytes
 {
     PT_CHECK_HANDLE(h);
     if (int rc = denoise_rendered(h)) return rc;
-    return denoise_copy_out(h, dst, row_pitch_bytes, h->dGuides, 32);
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->denoiseIntegratedValid ? h->denoiseSet[h->denoiseCurrent].guides : h->dGuides, 32);
 }
 
 PT_API int pt_denoise_read_variance(pt_handle h, float *dst, size_t row_pitch_bytes)
@@ -2379,6 +2467,49 @@ PT_API int pt_denoise_read_variance(pt_handle h, float *dst, size_t row_pitch_by
     if (!h->denoiseVarianceValid)
         return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render made no variance estimate (PT_DENOISE_FIXED, or iterations = 0)");
     return denoise_copy_out(h, dst, row_pitch_bytes, h->dVariance, 4);
+}
+
+PT_API int pt_denoise_set_temporal(pt_handle h, int enable, int max_history)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    if (enable != 0 && enable != 1) return fail(h, PT_E_BAD_ARGUMENT, "enable must be 0 or 1");
+    if (max_history < 1 || max_history > 65535) return fail(h, PT_E_OUT_OF_RANGE, "max_history 1..65535");
+    h->denoiseTemporal = enable; // (read by the next pt_denoise_render; what is queued already took its values)
+    h->denoiseMaxHistory = max_history;
+    return PT_OK;
+}
+
+PT_API int pt_denoise_history_clear(pt_handle h)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    for (pt_renderer::DenoiseSet &set : h->denoiseSet) set.valid = false; // (the buffers stay: a queued render may still read them)
+    h->denoiseHistoryUsed = false;
+    return PT_OK;
+}
+
+PT_API int pt_denoise_read_integrated(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    if (!h->denoiseIntegratedValid) return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render ran with the temporal stage off");
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->denoiseSet[h->denoiseCurrent].image, 16);
+}
+
+PT_API int pt_denoise_read_history(pt_handle h, float *image, void *guides, float out_B[9], float out_O[3])
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    if (!h->denoiseHistoryUsed) return fail(h, PT_E_BAD_ARGUMENT, "the last temporal pt_denoise_render had no history");
+    const pt_renderer::DenoiseSet &hist = h->denoiseSet[h->denoiseCurrent ^ 1];
+    if (image)
+        if (int rc = denoise_copy_out(h, image, 0, hist.image, 16)) return rc;
+    if (guides)
+        if (int rc = denoise_copy_out(h, guides, 0, hist.guides, 32)) return rc;
+    if (out_B) std::memcpy(out_B, hist.B, sizeof hist.B);
+    if (out_O) std::memcpy(out_O, hist.O, sizeof hist.O);
+    return PT_OK;
 }
 
 PT_API int pt_denoise_device_ptr(pt_handle h, void **out, size_t *bytes)
@@ -2403,15 +2534,20 @@ PT_API int pt_denoise_present_rgba8(pt_handle h, uint8_t *dst, size_t row_pitch_
 }
 
 // Timing aid (not declared in the public header): one stage of pt_denoise_render on its own — stage -1 = the guide kernel, i >= 0 = pass i
-// of the mode in force, -2 = stage V (the variance estimate; PT_DENOISE_VARIANCE only) — between the buffers a full render uses (a
-// pt_denoise_render must have run; the result it left is overwritten with a partial one).
+// of the mode in force, -2 = stage V (the variance estimate; PT_DENOISE_VARIANCE only), -4 = the temporal kernel (pt_denoise_set_temporal
+// on only) — between the buffers a full render uses (a pt_denoise_render must have run, with the temporal switch as it stands now; the
+// result it left is overwritten with a partial one; the sets are neither swapped nor marked).
 extern "C" __attribute__((visibility("default"))) int pt_debug_denoise_stage(pt_handle h, int guide_frame_index, int stage)
 {
     PT_CHECK_HANDLE(h);
     if (stage == kDenoiseStageV && (h->denoiseMode != PT_DENOISE_VARIANCE || h->denoiseIterations == 0))
         return fail(h, PT_E_BAD_ARGUMENT, "stage -2 needs PT_DENOISE_VARIANCE and iterations > 0");
-    if (guide_frame_index < 0 || stage < kDenoiseStageV || stage >= h->denoiseIterations) return fail(h, PT_E_BAD_ARGUMENT, "stage must be -2 .. iterations - 1");
+    if (stage == kDenoiseStageT && !h->denoiseTemporal) return fail(h, PT_E_BAD_ARGUMENT, "stage -4 needs pt_denoise_set_temporal on");
+    if (guide_frame_index < 0 || stage < kDenoiseStageT || stage == kDenoiseAll || stage >= h->denoiseIterations)
+        return fail(h, PT_E_BAD_ARGUMENT, "stage must be -4, -2 .. iterations - 1");
     if (int rc = denoise_rendered(h)) return rc;
+    if (h->denoiseIntegratedValid != (h->denoiseTemporal != 0))
+        return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render ran with another setting of pt_denoise_set_temporal");
     return denoise_run(h, guide_frame_index, stage);
 }
 

@@ -359,4 +359,89 @@ hipError_t launch_atrous_var(const AtrousVarArgs &a, hipStream_t stream)
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------- temporal stage (pt_denoise_set_temporal)
+// I(p) = the image's (C, n) blended with the history set's I reprojected to p: the guide position of p goes through the
+// history camera's inverse ray matrix B to a point (fx, fy) of the history image, whose 2x2 neighbours of p's id are weighted by the
+// bilinear weight and the a-trous filter's own normal and plane weights (same expressions, same order), and the weighted mean (colour Hc,
+// count m clamped to max_history) is mixed with C by sample counts: I = ((n C + m' Hc) / (n + m'), n + m').  One pixel per lane, 64x4
+// tiles as pt_atrous_kernel<0>: a wavefront is 64 adjacent pixels of one row, so the centre's three 16-byte loads coalesce; the four taps
+// are data-dependent gathers — G0 first, G1 and I_h only where the id matches.  Every comparison is false for NaN, so a pixel whose
+// projection is not finite passes through.  fx lies in [-1, W) where taps are formed, so x0 = floor(fx) fits an int and every tap is
+// bounds-checked before its load.
+// TAPS = 2, the footprint's width: a template so that the kernel is emitted behind the others and leaves their code as it was.
+template <int TAPS>
+__global__ __launch_bounds__(256) void pt_temporal_kernel(const TemporalArgs a)
+{
+    static_assert(TAPS == 2, "the definition's 2x2 bilinear footprint");
+    const int tid = threadIdx.x;
+    const int px = blockIdx.x * 64 + (tid & 63), py = blockIdx.y * 4 + (tid >> 6);
+    if (px >= a.width || py >= a.height) return;
+    const size_t center = (size_t)py * a.width + px;
+    const float4 cp = a.colIn[center];
+    float4 out = make_float4(cp.x, cp.y, cp.z, a.n);
+    if (a.histImage) { // (uniform: a valid history set)
+        const float4 g0p = a.guides[2 * center];
+        const float4 g1p = a.guides[2 * center + 1];
+        const int idp = __float_as_int(g0p.w);
+        const float dx = g0p.x - a.O[0], dy = g0p.y - a.O[1], dz = g0p.z - a.O[2];
+        const float x = (a.B[0] * dx + a.B[1] * dy) + a.B[2] * dz;
+        const float y = (a.B[3] * dx + a.B[4] * dy) + a.B[5] * dz;
+        const float z = (a.B[6] * dx + a.B[7] * dy) + a.B[8] * dz;
+        const float fw = (float)a.width, fh = (float)a.height;
+        const float fx = ((x / z) * 0.5f + 0.5f) * fw - 0.5f;
+        const float fy = ((y / z) * 0.5f + 0.5f) * fh - 0.5f;
+        if (idp != -1 && z > 0.0f && fx >= -1.0f && fx < fw && fy >= -1.0f && fy < fh) {
+            const float flx = __builtin_floorf(fx), fly = __builtin_floorf(fy);
+            const float ax = fx - flx, ay = fy - fly;
+            const int x0 = (int)flx, y0 = (int)fly;
+            const float planeDen = a.sigmaPlane * g1p.w;
+            float Wh = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, Mh = 0.0f;
+#pragma unroll
+            for (int j = 0; j < TAPS; j++) {
+#pragma unroll
+                for (int i = 0; i < TAPS; i++) {
+                    const int qx = x0 + i, qy = y0 + j;
+                    if (qx < 0 || qx >= a.width || qy < 0 || qy >= a.height) continue;
+                    const size_t at = (size_t)qy * a.width + qx;
+                    const float4 g0q = a.histGuides[2 * at];
+                    if (__float_as_int(g0q.w) != idp) continue;
+                    const float4 g1q = a.histGuides[2 * at + 1];
+                    const float4 hq = a.histImage[at];
+                    const float bw = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+                    const float d = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
+                    float wn = d > 0.0f ? d : 0.0f;
+                    for (int k = 0; k < a.normalPower; k++) wn = wn * wn;
+                    const float ex = g0q.x - g0p.x, ey = g0q.y - g0p.y, ez = g0q.z - g0p.z;
+                    const float e = (g1p.x * ex + g1p.y * ey) + g1p.z * ez;
+                    const float r = e / planeDen;
+                    const float zz = 1.0f - r * r;
+                    const float wz = zz > 0.0f ? zz : 0.0f;
+                    const float w = (bw * wn) * wz;
+                    Wh = Wh + w;
+                    Sr = Sr + w * hq.x;
+                    Sg = Sg + w * hq.y;
+                    Sb = Sb + w * hq.z;
+                    Mh = Mh + w * hq.w;
+                }
+            }
+            if (Wh > 0.0f) {
+                const float m = Mh / Wh;
+                const float mc = m < a.maxHistory ? m : a.maxHistory;
+                const float den = a.n + mc;
+                if (den > 0.0f)
+                    out = make_float4((a.n * cp.x + mc * (Sr / Wh)) / den, (a.n * cp.y + mc * (Sg / Wh)) / den,
+                                      (a.n * cp.z + mc * (Sb / Wh)) / den, den);
+            }
+        }
+    }
+    a.out[center] = out;
+}
+
+hipError_t launch_temporal(const TemporalArgs &a, hipStream_t stream)
+{
+    if (a.width < 1 || a.height < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_temporal_kernel<2>, dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
 } // namespace pt

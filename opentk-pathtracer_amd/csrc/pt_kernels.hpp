@@ -264,6 +264,23 @@ struct AtrousVarArgs {
     int last;         // the last pass writes alpha 1
 };
 hipError_t launch_atrous_var(const AtrousVarArgs &a, hipStream_t stream);
+// the temporal stage (pt_denoise_set_temporal): out = (colIn.rgb, n) blended per pixel with the history image reprojected through the
+// guides' world positions and the history's camera; out's alpha = the pixel's sample count.  histImage == null: no valid history
+struct TemporalArgs {
+    const float4 *colIn;      // the accumulation image; alpha is not read
+    const float4 *guides;     // of the current view
+    const float4 *histImage;  // I of the history set (rgb, count), or null
+    const float4 *histGuides;
+    float4 *out;              // I of the current set
+    int width, height;
+    float n;                  // (float)(frame index * spp): the samples colIn holds
+    float maxHistory;         // max_history as a float (1 .. 65535: exact)
+    float B[9];               // the history camera's inverse ray matrix, row-major: B (P - O) = lambda (ndcx, ndcy, 1)
+    float O[3];               // the history camera's ray origin
+    float sigmaPlane;
+    int normalPower;
+};
+hipError_t launch_temporal(const TemporalArgs &a, hipStream_t stream);
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 // the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);

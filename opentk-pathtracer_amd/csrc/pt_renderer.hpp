@@ -182,6 +182,23 @@ struct pt_renderer {
     float denoiseSigmaVariance = 6.0f;
     float *dVariance = nullptr;
     bool denoiseVarianceValid = false;
+    // Temporal stage (pt_denoise_set_temporal).  A set = one integrated image (rgb, count), one guide buffer (beside dGuides, which the
+    // renders with the stage off keep to themselves), the camera it was made under (B = the inverse of the ray matrix, O = the ray
+    // origin), the reset epoch it was made in and a valid flag.  denoiseSet[denoiseCurrent] is the current set, the other one the
+    // history; both allocated by the first temporal pt_denoise_render after a (re)size or (re)tiling and freed with the buffers above —
+    // never on the pt_render path.  resetEpoch: bumped by pt_reset, pt_write_result, pt_set_size, pt_set_tile, pt_set_interleaved_tile.
+    struct DenoiseSet {
+        float4 *image = nullptr, *guides = nullptr;
+        float B[9] = {0}, O[3] = {0};
+        unsigned long long epoch = 0;
+        bool valid = false;
+    };
+    DenoiseSet denoiseSet[2];
+    int denoiseCurrent = 0;
+    unsigned long long resetEpoch = 0;
+    int denoiseTemporal = 0, denoiseMaxHistory = 32;
+    bool denoiseIntegratedValid = false; // the last pt_denoise_render ran with the stage on (its I and guides are the current set's) ...
+    bool denoiseHistoryUsed = false;     // ... and read a valid history set
 
     // hand-over audit (only allocated by the -DPT_AUDIT build, see pt_debug_hooks.hpp): side word per accumulation pixel + violation log
     unsigned long long *dAudit = nullptr;

@@ -360,6 +360,32 @@ public:
         Check(pt_denoise_read_variance(h_, var.data(), 0), h_);
         return var;
     }
+    // the temporal stage for the Denoise() calls that follow: the previous view's result is carried across a ResetRenderer() by
+    // reprojecting it through the guides and blending by sample counts; maxHistory (1..65535) caps the count a history pixel brings along
+    void SetDenoiseTemporal(bool enable = true, int maxHistory = 32) { Check(pt_denoise_set_temporal(h_, enable ? 1 : 0, maxHistory), h_); }
+    // forget what the temporal stage integrated: after a scene, material or environment edit
+    void ClearDenoiseHistory() { Check(pt_denoise_history_clear(h_), h_); }
+    // the integrated image of the last Denoise() with the temporal stage on: RGBA32F, alpha = the per-pixel sample count, row 0 = bottom
+    std::vector<float> DenoiseIntegrated() const
+    {
+        std::vector<float> img((size_t)width_ * height_ * 4);
+        Check(pt_denoise_read_integrated(h_, img.data(), 0), h_);
+        return img;
+    }
+    // the history set the last temporal Denoise() used: its integrated image, its guide records and its camera (B row-major, O)
+    struct DenoiseHistorySet {
+        std::vector<float> image;
+        std::vector<GuideRecord> guides;
+        float B[9], O[3];
+    };
+    DenoiseHistorySet DenoiseHistory() const
+    {
+        DenoiseHistorySet s;
+        s.image.resize((size_t)width_ * height_ * 4);
+        s.guides.resize((size_t)width_ * height_);
+        Check(pt_denoise_read_history(h_, s.image.data(), s.guides.data(), s.B, s.O), h_);
+        return s;
+    }
     // ScreenEffect.Render (src/Render/ScreenEffect.cs:29-37) of the last Denoise() instead of `Result`
     std::vector<uint8_t> PresentDenoised() const
     {

@@ -224,6 +224,10 @@ def load() -> C.CDLL:
         "pt_denoise_present_rgba8": [vp, C.POINTER(C.c_uint8), C.c_size_t],
         "pt_denoise_set_mode": [vp, C.c_int, C.c_float],
         "pt_denoise_read_variance": [vp, fp, C.c_size_t],
+        "pt_denoise_set_temporal": [vp, C.c_int, C.c_int],
+        "pt_denoise_history_clear": [vp],
+        "pt_denoise_read_integrated": [vp, fp, C.c_size_t],
+        "pt_denoise_read_history": [vp, fp, vp, fp, fp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -283,7 +287,8 @@ def debug_handover_stats(handle) -> dict:
 
 def debug_denoise_stage(handle, frame: int, stage: int) -> None:
     """One stage of pt_denoise_render on its own, for timing (pt_debug_denoise_stage — exported, not in the public header): stage -1 = the
-    guide kernel, i >= 0 = pass i of the mode in force, -2 = the variance estimate (PT_DENOISE_VARIANCE only).  A pt_denoise_render must have run; the result it left is overwritten with a partial one."""
+    guide kernel, i >= 0 = pass i of the mode in force, -2 = the variance estimate (PT_DENOISE_VARIANCE only), -4 = the temporal kernel
+    (pt_denoise_set_temporal on only).  A pt_denoise_render must have run; the result it left is overwritten with a partial one."""
     L = load()
     L.pt_debug_denoise_stage.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pt_debug_denoise_stage.restype = C.c_int

@@ -326,6 +326,33 @@ class PathTracer:
         check(self._lib.pt_denoise_read_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
         return out
 
+    def SetDenoiseTemporal(self, enable: bool = True, max_history: int = 32) -> None:
+        """pt_denoise_set_temporal: the Denoise calls that follow carry the previous view's result across a ResetRenderer by reprojecting
+        it through the guides and blending by sample counts; max_history (1..65535) caps the count a history pixel brings along."""
+        check(self._lib.pt_denoise_set_temporal(self._h, int(enable), max_history), self._h)
+
+    def ClearDenoiseHistory(self) -> None:
+        """pt_denoise_history_clear: forget what the temporal stage integrated (after a scene, material or environment edit)."""
+        check(self._lib.pt_denoise_history_clear(self._h), self._h)
+
+    def DenoiseIntegrated(self) -> np.ndarray:
+        """pt_denoise_read_integrated: the integrated image of the last Denoise with the temporal stage on as (rows, Width, 4) float32;
+        alpha = the per-pixel sample count."""
+        out = np.empty((self.rows, self.Width, 4), dtype=np.float32)
+        check(self._lib.pt_denoise_read_integrated(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
+        return out
+
+    def DenoiseHistory(self):
+        """pt_denoise_read_history: the history set the last temporal Denoise used -> (image (rows, Width, 4) float32, guides (rows, Width)
+        GUIDE_DTYPE, B (3, 3) float32, O (3,) float32): B (P - O) = lambda (ndc x, ndc y, 1) for a point P that view saw."""
+        image = np.empty((self.rows, self.Width, 4), dtype=np.float32)
+        guides = np.empty((self.rows, self.Width), dtype=GUIDE_DTYPE)
+        B, O = np.empty((3, 3), dtype=np.float32), np.empty(3, dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        check(self._lib.pt_denoise_read_history(self._h, image.ctypes.data_as(fp), guides.ctypes.data_as(C.c_void_p), B.ctypes.data_as(fp),
+                                                O.ctypes.data_as(fp)), self._h)
+        return image, guides, B, O
+
     def PresentDenoised(self) -> np.ndarray:
         """pt_denoise_present_rgba8: the result of the last Denoise through the tone map Present applies, as (rows, Width, 4) uint8."""
         out = np.empty((self.rows, self.Width, 4), dtype=np.uint8)
