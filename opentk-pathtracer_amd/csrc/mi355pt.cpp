@@ -52,6 +52,7 @@ int bind_device(pt_handle h)
 } // namespace ptimpl
 
 using ptimpl::bind_device;
+using ptimpl::ensure_rgba8;
 using ptimpl::fail;
 using ptimpl::flush_frames;
 using ptimpl::hip_fail;
@@ -286,42 +287,6 @@ int ensure_stripe(pt_handle h, int j)
 }
 
 hipStream_t stripe_stream(pt_handle h, int j) { return j == 0 ? h->stream : h->stripeStream[j]; }
-
-int free_first_hit(pt_handle h)
-{
-    if (!h->dFirstHit) return PT_OK;
-    PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_first_hit_render may still write it)
-    PT_HIP(h, hipFree(h->dFirstHit));
-    h->dFirstHit = nullptr;
-    return PT_OK;
-}
-
-int free_denoise(pt_handle h)
-{
-    h->denoiseResult = -1;
-    h->denoiseVarianceValid = false;
-    h->denoiseIntegratedValid = h->denoiseHistoryUsed = false;
-    for (pt_renderer::DenoiseSet &set : h->denoiseSet) set.valid = false;
-    if (!h->dGuides && !h->dDenoise[0] && !h->dDenoise[1] && !h->dVariance && !h->denoiseSet[0].image && !h->denoiseSet[0].guides &&
-        !h->denoiseSet[1].image && !h->denoiseSet[1].guides)
-        return PT_OK;
-    PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_denoise_render may still write them)
-    if (h->dGuides) PT_HIP(h, hipFree(h->dGuides));
-    h->dGuides = nullptr;
-    if (h->dVariance) PT_HIP(h, hipFree(h->dVariance));
-    h->dVariance = nullptr;
-    for (float4 *&img : h->dDenoise) {
-        if (img) PT_HIP(h, hipFree(img));
-        img = nullptr;
-    }
-    for (pt_renderer::DenoiseSet &set : h->denoiseSet) {
-        if (set.image) PT_HIP(h, hipFree(set.image));
-        set.image = nullptr;
-        if (set.guides) PT_HIP(h, hipFree(set.guides));
-        set.guides = nullptr;
-    }
-    return PT_OK;
-}
 } // namespace ptimpl
 
 namespace {
@@ -386,6 +351,27 @@ int clear_accum(pt_handle h)
     PT_HIP(h, pt::launch_clear(h->accum(), h->tilePixels(), h->stream));
     h->tagsLive = false;
     return audit_forget(h);
+}
+
+// What pt_set_size, pt_set_tile and pt_set_interleaved_tile share.  Before the new size or tiling is stored: the launches so far — and their
+// hand-over repair passes — belong to the buffers as they are, the first-hit records and the denoiser's buffers to the size and tiling ...
+int leave_tiling(pt_handle h)
+{
+    if (int rc = join_stripes(h)) return rc;
+    if (int rc = ptimpl::free_first_hit(h)) return rc;
+    if (int rc = ptimpl::free_denoise(h)) return rc;
+    h->resetEpoch++;
+    return PT_OK;
+}
+
+// ... and behind it: frame 0 of a cleared image of the new rows
+int enter_tiling(pt_handle h)
+{
+    h->frame = 0; // PathTracer.cs:133
+    h->tileMasksValid = false;
+    h->launchesSinceInputChange = 0;
+    if (int rc = ensure_accum(h)) return rc;
+    return clear_accum(h);
 }
 
 } // namespace
@@ -572,14 +558,7 @@ PT_API int pt_destroy(pt_handle h)
     if (h->dRgba8) (void)hipFree(h->dRgba8);
     if (h->dFirstHit) (void)hipFree(h->dFirstHit);
     if (h->dPick) (void)hipFree(h->dPick);
-    if (h->dGuides) (void)hipFree(h->dGuides);
-    if (h->dVariance) (void)hipFree(h->dVariance);
-    if (h->dDenoise[0]) (void)hipFree(h->dDenoise[0]);
-    if (h->dDenoise[1]) (void)hipFree(h->dDenoise[1]);
-    for (pt_renderer::DenoiseSet &set : h->denoiseSet) {
-        if (set.image) (void)hipFree(set.image);
-        if (set.guides) (void)hipFree(set.guides);
-    }
+    (void)h->denoise.release();
     if (h->dTimeline) (void)hipFree(h->dTimeline);
     if (h->evBegin) (void)hipEventDestroy(h->evBegin);
     if (h->evEnd) (void)hipEventDestroy(h->evEnd);
@@ -598,20 +577,13 @@ PT_API int pt_set_size(pt_handle h, int width, int height)
     if (h->isGroup()) return ptimpl::group_set_size(h, width, height);
     if (int rc = flush_frames(h)) return rc; // pending frames were rendered with the inputs as they were
     if (int rc = bind_device(h)) return rc;
-    if (int rc = join_stripes(h)) return rc; // (the launches so far — and their hand-over repair passes — belong to the buffers as they are)
-    if (int rc = ptimpl::free_first_hit(h)) return rc;
-    if (int rc = ptimpl::free_denoise(h)) return rc;
-    h->resetEpoch++;
+    if (int rc = leave_tiling(h)) return rc;
     h->width = width;
     h->height = height;
     h->y0 = 0;
     h->rows = height;
     h->bandRows = 0;
-    h->frame = 0; // PathTracer.cs:133
-    h->tileMasksValid = false;
-    h->launchesSinceInputChange = 0;
-    if (int rc = ensure_accum(h)) return rc;
-    return clear_accum(h);
+    return enter_tiling(h);
 }
 
 PT_API int pt_set_tile(pt_handle h, int y0, int rows)
@@ -621,18 +593,11 @@ PT_API int pt_set_tile(pt_handle h, int y0, int rows)
     if (int rc = flush_frames(h)) return rc; // pending frames were rendered with the inputs as they were
     if (y0 < 0 || rows <= 0 || y0 + rows > h->height) return fail(h, PT_E_BAD_ARGUMENT, "tile outside the image");
     if (int rc = bind_device(h)) return rc;
-    if (int rc = join_stripes(h)) return rc; // (see pt_set_size)
-    if (int rc = ptimpl::free_first_hit(h)) return rc;
-    if (int rc = ptimpl::free_denoise(h)) return rc;
-    h->resetEpoch++;
+    if (int rc = leave_tiling(h)) return rc;
     h->y0 = y0;
     h->rows = rows;
     h->bandRows = 0;
-    h->frame = 0;
-    h->tileMasksValid = false;
-    h->launchesSinceInputChange = 0;
-    if (int rc = ensure_accum(h)) return rc;
-    return clear_accum(h);
+    return enter_tiling(h);
 }
 
 PT_API int pt_set_interleaved_tile(pt_handle h, int rank, int world, int band_rows)
@@ -650,33 +615,14 @@ PT_API int pt_set_interleaved_tile(pt_handle h, int rank, int world, int band_ro
         rows += (top < h->height ? top : h->height) - b * band_rows;
     }
     if (rows <= 0) return fail(h, PT_E_BAD_ARGUMENT, "this rank owns no rows (image too small for world * band_rows)");
-    if (int rc = join_stripes(h)) return rc; // (see pt_set_size)
-    if (int rc = ptimpl::free_first_hit(h)) return rc;
-    if (int rc = ptimpl::free_denoise(h)) return rc;
-    h->resetEpoch++;
+    if (int rc = leave_tiling(h)) return rc;
     h->y0 = 0;
     h->rows = (int)rows;
     h->bandRows = band_rows;
     h->bandWorld = world;
     h->bandRank = rank;
-    h->frame = 0;
-    h->tileMasksValid = false;
-    h->launchesSinceInputChange = 0;
-    if (int rc = ensure_accum(h)) return rc;
-    return clear_accum(h);
+    return enter_tiling(h);
 }
-
-// group handles: replicate a call to every part; the first failure is reported on the group handle
-#define PT_FAN_OUT(h, call)                                                                                            \
-    do {                                                                                                               \
-        if ((h)->isGroup()) {                                                                                          \
-            for (pt_handle part : (h)->parts) {                                                                        \
-                int rc_ = (call);                                                                                      \
-                if (rc_ != PT_OK) return fail((h), rc_, part->error);                                                  \
-            }                                                                                                          \
-            return PT_OK;                                                                                              \
-        }                                                                                                              \
-    } while (0)
 
 PT_API int pt_reset(pt_handle h)
 {
@@ -1373,6 +1319,10 @@ bool gpu_busy(pt_handle h)
     return busy;
 }
 
+} // namespace
+
+namespace ptimpl {
+
 int ensure_rgba8(pt_handle h)
 {
     size_t need = h->tilePixels();
@@ -1388,10 +1338,6 @@ int ensure_rgba8(pt_handle h)
     }
     return PT_OK;
 }
-
-} // namespace
-
-namespace ptimpl {
 
 // frames one launch may hold for this handle right now (pt_set_frame_batch; automatic: 64, or 256 on a small share)
 int batch_limit(pt_handle h)
@@ -2131,424 +2077,6 @@ PT_API int pt_timer_end(pt_handle h, float *out_ms)
     PT_HIP(h, hipEventSynchronize(h->evEnd));
     PT_HIP(h, hipEventElapsedTime(out_ms, h->evBegin, h->evEnd));
     return PT_OK;
-}
-
-// ---- first-hit query (pt_first_hit.hip): what src/Render/Gui.cs:223-233 -> src/MainWindow.cs:302-318 answer on the CPU, for the ray the
-// integrator traces.  Reads the camera shadow, the scene blob and the parameters; touches neither the accumulation image, the frame
-// counter, the cached tile masks, the environment nor an arithmetic switch.
-static_assert(pt::kFirstHitCuboidBase == PT_MAX_SPHERES, "first-hit ids: cuboid j is PT_MAX_SPHERES + j");
-
-// the kernel argument of a first-hit launch over this handle's rows (only the fields stage_scene, primary_ray and global_row read)
-static void first_hit_args(pt_handle h, pt::FrameArgs &a, int frame_index)
-{
-    std::memset(&a, 0, sizeof a);
-    std::memcpy(a.invProj, h->basic, 64);
-    std::memcpy(a.invView, h->basic + 64, 64);
-    std::memcpy(a.viewPos, h->basic + 128, 12);
-    a.focalLength = h->focalLength;
-    a.apertureDiameter = h->apertureDiameter;
-    a.width = h->width;
-    a.height = h->height;
-    a.invW = 1.0f / (float)h->width; // (as fill_frame_args)
-    a.invH = 1.0f / (float)h->height;
-    a.y0 = h->y0;
-    a.rows = h->rows;
-    a.bandRows = h->bandRows;
-    a.bandWorld = h->bandWorld;
-    a.bandRank = h->bandRank;
-    a.numSpheres = h->numSpheres;
-    a.numCuboids = h->numCuboids;
-    a.rayDepth = 1;
-    a.spp = 1;
-    a.batchFrames = 1;
-    a.frame = frame_index;
-    a.objects = h->dObjects;
-    a.tilesX = (h->width + 7) / 8;
-    a.tilesY = (h->rows + 7) / 8;
-}
-
-PT_API int pt_first_hit_render(pt_handle h, int frame_index)
-{
-    PT_CHECK_HANDLE(h);
-    if (frame_index < 0) return fail(h, PT_E_BAD_ARGUMENT, "frame_index must be >= 0");
-    PT_FAN_OUT(h, pt_first_hit_render(part, frame_index));
-    if (int rc = bind_device(h)) return rc;
-    if (int rc = join_stripes(h)) return rc; // (pending frames are launched, an open frame-fed launch is closed: like every non-render entry point)
-    if (!h->dFirstHit) PT_HIP(h, hipMalloc((void **)&h->dFirstHit, h->tilePixels() * 2 * sizeof(float4)));
-    pt::FrameArgs a;
-    first_hit_args(h, a, frame_index);
-    PT_HIP(h, pt::launch_first_hit(a, h->dFirstHit, -1, h->stream));
-    return PT_OK;
-}
-
-PT_API int pt_first_hit_read(pt_handle h, void *dst, size_t row_pitch_bytes)
-{
-    PT_CHECK_HANDLE(h);
-    if (!dst) return fail(h, PT_E_BAD_ARGUMENT, "dst == NULL");
-    const size_t rowBytes = (size_t)h->width * 32;
-    if (row_pitch_bytes == 0) row_pitch_bytes = rowBytes;
-    if (row_pitch_bytes < rowBytes) return fail(h, PT_E_BAD_ARGUMENT, "row pitch smaller than a row");
-    if (h->isGroup()) return ptimpl::group_first_hit_read(h, dst, row_pitch_bytes);
-    if (!h->dFirstHit) return fail(h, PT_E_BAD_ARGUMENT, "no pt_first_hit_render since the last pt_set_size / pt_set_tile / pt_set_interleaved_tile");
-    if (int rc = bind_device(h)) return rc;
-    PT_HIP(h, hipMemcpy2DAsync(dst, row_pitch_bytes, h->dFirstHit, rowBytes, rowBytes, (size_t)h->rows, hipMemcpyDeviceToHost, h->stream));
-    PT_HIP(h, hipStreamSynchronize(h->stream));
-    return PT_OK;
-}
-
-PT_API int pt_first_hit_device_ptr(pt_handle h, void **out, size_t *bytes)
-{
-    PT_CHECK_HANDLE(h);
-    if (h->isGroup()) return fail(h, PT_E_BAD_ARGUMENT, "pt_first_hit_device_ptr is not available on a group handle");
-    if (!h->dFirstHit) return fail(h, PT_E_BAD_ARGUMENT, "no pt_first_hit_render since the last pt_set_size / pt_set_tile / pt_set_interleaved_tile");
-    if (out) *out = h->dFirstHit;
-    if (bytes) *bytes = h->tilePixels() * 2 * sizeof(float4);
-    return PT_OK;
-}
-
-PT_API int pt_pick(pt_handle h, int x, int y, int frame_index, int *out_id, float *out_t, float out_origin[3], float out_dir[3])
-{
-    PT_CHECK_HANDLE(h);
-    if (!out_id) return fail(h, PT_E_BAD_ARGUMENT, "out_id == NULL");
-    if (frame_index < 0) return fail(h, PT_E_BAD_ARGUMENT, "frame_index must be >= 0");
-    if (x < 0 || x >= h->width || y < 0 || y >= h->height) return fail(h, PT_E_OUT_OF_RANGE, "pixel outside the image");
-    if (h->isGroup()) return ptimpl::group_pick(h, x, y, frame_index, out_id, out_t, out_origin, out_dir);
-    // image row -> row inside this handle's storage (the inverse of the kernels' global_row)
-    int ly;
-    if (h->bandRows == 0) {
-        ly = y - h->y0;
-    } else {
-        const int band = y / h->bandRows;
-        ly = band % h->bandWorld == h->bandRank ? (band / h->bandWorld) * h->bandRows + y % h->bandRows : -1;
-    }
-    if (ly < 0 || ly >= h->rows) return fail(h, PT_E_OUT_OF_RANGE, "this handle does not own the pixel's row (pt_set_tile / pt_set_interleaved_tile)");
-    if (int rc = bind_device(h)) return rc;
-    if (int rc = join_stripes(h)) return rc;
-    if (!h->dPick) PT_HIP(h, hipMalloc((void **)&h->dPick, 64 * 2 * sizeof(float4)));
-    pt::FrameArgs a;
-    first_hit_args(h, a, frame_index);
-    PT_HIP(h, pt::launch_first_hit(a, h->dPick, (ly >> 3) * a.tilesX + (x >> 3), h->stream));
-    float rec[8];
-    PT_HIP(h, hipMemcpyAsync(rec, h->dPick + 2 * ((ly & 7) * 8 + (x & 7)), sizeof rec, hipMemcpyDeviceToHost, h->stream));
-    PT_HIP(h, hipStreamSynchronize(h->stream));
-    std::memcpy(out_id, &rec[7], sizeof(int));
-    if (out_t) *out_t = rec[3];
-    if (out_origin) std::memcpy(out_origin, &rec[0], 12);
-    if (out_dir) std::memcpy(out_dir, &rec[4], 12);
-    return PT_OK;
-}
-
-// ---- preview denoiser (pt_denoise.hip): guides from the integrator's own primary ray + an edge-avoiding a-trous filter of
-// the accumulation image, for the first frames after the reset that every camera move and GUI edit causes (MainWindow.cs:49-63); the
-// result goes through the tone map of ScreenEffect.cs:29-37.  Reads the image (RGB), the camera shadow, the scene blob and the parameters;
-// touches neither the accumulation image, the frame counter, the environment nor an arithmetic switch.
-static int denoise_owner(pt_handle h)
-{
-    if (h->isGroup()) return fail(h, PT_E_BAD_ARGUMENT, "the denoiser is not available on a group handle");
-    if (h->rows != h->height || h->bandRows != 0)
-        return fail(h, PT_E_BAD_ARGUMENT, "the denoiser needs a handle that owns the whole image (pt_set_tile / pt_set_interleaved_tile in force)");
-    return PT_OK;
-}
-
-// The camera of a set: the ray generator is linear in the NDC point, wd = A (ndcx, ndcy, 1) with A = [a b c] formed
-// from the blob's InvProjection m and InvView v (compute.glsl:352-357 as primary_ray_cam evaluates it); B = A^-1, formed and inverted in
-// double and rounded to binary32 once, O = InvView's translation.  false: A is singular or B not finite.
-static bool denoise_set_camera(const unsigned char *basic, float B[9], float O[3])
-{
-    float m[16], v[16];
-    std::memcpy(m, basic, 64);
-    std::memcpy(v, basic + 64, 64);
-    double A[3][3];
-    for (int r = 0; r < 3; r++) {
-        A[r][0] = (double)v[r] * m[0] + (double)v[4 + r] * m[1];
-        A[r][1] = (double)v[r] * m[4] + (double)v[4 + r] * m[5];
-        A[r][2] = -((double)v[r] * m[8] + (double)v[4 + r] * m[9]) - (double)v[8 + r];
-        O[r] = v[12 + r];
-    }
-    double C[3][3]; // cofactors: A^-1 = C^T / det
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-            C[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1];
-        }
-    const double det = A[0][0] * C[0][0] + A[0][1] * C[0][1] + A[0][2] * C[0][2];
-    bool ok = std::isfinite(det) && det != 0.0;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            B[3 * i + j] = (float)(C[j][i] / det);
-            ok = ok && std::isfinite(B[3 * i + j]);
-        }
-    return ok;
-}
-
-// stage kDenoiseAll: everything; -1: the guides only; kDenoiseStageV: stage V of the variance mode only; kDenoiseStageT: the temporal
-// kernel only; i >= 0: pass i only (pt_debug_denoise_stage, for timing)
-constexpr int kDenoiseStageV = -2, kDenoiseAll = -3, kDenoiseStageT = -4;
-static int denoise_run(pt_handle h, int guide_frame_index, int stage)
-{
-    if (int rc = bind_device(h)) return rc;
-    // (the preamble of pt_postprocess_device: pending frames are launched, an open frame-fed launch is closed, an abandoned hand-over is repaired)
-    if (int rc = join_stripes(h)) return rc;
-    const size_t pixels = h->tilePixels();
-    const bool variance = h->denoiseMode == PT_DENOISE_VARIANCE;
-    const bool temporal = h->denoiseTemporal != 0;
-    if (!temporal && !h->dGuides) PT_HIP(h, hipMalloc((void **)&h->dGuides, pixels * 2 * sizeof(float4)));
-    for (float4 *&img : h->dDenoise)
-        if (!img) PT_HIP(h, hipMalloc((void **)&img, pixels * sizeof(float4)));
-    if (variance && !h->dVariance) PT_HIP(h, hipMalloc((void **)&h->dVariance, pixels * sizeof(float)));
-    if (temporal) {
-        for (pt_renderer::DenoiseSet &set : h->denoiseSet) {
-            if (!set.image) PT_HIP(h, hipMalloc((void **)&set.image, pixels * sizeof(float4)));
-            if (!set.guides) PT_HIP(h, hipMalloc((void **)&set.guides, pixels * 2 * sizeof(float4)));
-        }
-        // a current set of an earlier reset epoch becomes the history: a pointer swap (a timing stage works between the sets as they are)
-        if (stage == kDenoiseAll && h->denoiseSet[h->denoiseCurrent].valid && h->denoiseSet[h->denoiseCurrent].epoch != h->resetEpoch) {
-            h->denoiseCurrent ^= 1;
-            h->denoiseSet[h->denoiseCurrent].valid = false; // (until this render has made it)
-        }
-    }
-    pt_renderer::DenoiseSet &cur = h->denoiseSet[h->denoiseCurrent];
-    const pt_renderer::DenoiseSet &hist = h->denoiseSet[h->denoiseCurrent ^ 1];
-    float4 *const guides = temporal ? cur.guides : h->dGuides; // the guides of this render ...
-    const float4 *const first = temporal ? cur.image : h->accum(); // ... and C_0, the input of stage V and of pass 0
-    if (stage == kDenoiseAll || stage == -1) {
-        pt::FrameArgs a;
-        first_hit_args(h, a, guide_frame_index);
-        PT_HIP(h, pt::launch_guides(a, guides, h->stream));
-        if (stage == -1) return PT_OK;
-    }
-    if (temporal && (stage == kDenoiseAll || stage == kDenoiseStageT)) {
-        pt::TemporalArgs t;
-        t.colIn = h->accum();
-        t.guides = guides;
-        t.histImage = hist.valid ? hist.image : nullptr;
-        t.histGuides = hist.guides;
-        t.out = cur.image;
-        t.width = h->width;
-        t.height = h->rows;
-        t.n = (float)((long long)h->frame * h->spp);
-        t.maxHistory = (float)h->denoiseMaxHistory;
-        std::memcpy(t.B, hist.B, sizeof t.B);
-        std::memcpy(t.O, hist.O, sizeof t.O);
-        t.sigmaPlane = h->denoiseSigmaPlane;
-        t.normalPower = h->denoiseNormalPower;
-        PT_HIP(h, pt::launch_temporal(t, h->stream));
-        if (stage == kDenoiseStageT) return PT_OK;
-        cur.valid = denoise_set_camera(h->basic, cur.B, cur.O);
-        cur.epoch = h->resetEpoch;
-        h->denoiseHistoryUsed = hist.valid;
-    }
-    if (stage == kDenoiseAll) h->denoiseIntegratedValid = temporal;
-    const int n = h->denoiseIterations;
-    if (n == 0 && stage == kDenoiseAll) PT_HIP(h, pt::launch_denoise_copy(first, h->dDenoise[0], pixels, h->stream));
-    if (variance) {
-        if (n > 0 && (stage == kDenoiseAll || stage == kDenoiseStageV)) {
-            pt::VarianceArgs v;
-            v.colIn = first;
-            v.guides = guides;
-            v.var = h->dVariance;
-            v.width = h->width;
-            v.height = h->rows;
-            PT_HIP(h, pt::launch_variance(v, h->stream));
-        }
-        for (int i = 0; i < n && stage != kDenoiseStageV; i++) {
-            if (stage >= 0 && i != stage) continue;
-            pt::AtrousVarArgs t;
-            t.colIn = i == 0 ? first : h->dDenoise[(i - 1) & 1];
-            t.varIn = i == 0 ? h->dVariance : nullptr;
-            t.guides = guides;
-            t.colOut = h->dDenoise[i & 1];
-            t.width = h->width;
-            t.height = h->rows;
-            t.step = 1 << i;
-            t.k2 = h->denoiseSigmaVariance * h->denoiseSigmaVariance;
-            t.sigmaPlane = h->denoiseSigmaPlane;
-            t.normalPower = h->denoiseNormalPower;
-            t.last = i == n - 1;
-            PT_HIP(h, pt::launch_atrous_var(t, h->stream));
-        }
-        if (stage == kDenoiseAll) {
-            h->denoiseResult = n == 0 ? 0 : (n - 1) & 1;
-            h->denoiseVarianceValid = n > 0;
-        }
-        return PT_OK;
-    }
-    for (int i = 0; i < n; i++) {
-        if (stage >= 0 && i != stage) continue;
-        pt::AtrousArgs t;
-        t.colIn = i == 0 ? first : h->dDenoise[(i - 1) & 1];
-        t.guides = guides;
-        t.colOut = h->dDenoise[i & 1];
-        t.width = h->width;
-        t.height = h->rows;
-        t.step = 1 << i;
-        t.invSigma = 1.0f / (h->denoiseSigmaColor * std::ldexp(1.0f, -i));
-        t.sigmaPlane = h->denoiseSigmaPlane;
-        t.normalPower = h->denoiseNormalPower;
-        PT_HIP(h, pt::launch_atrous(t, h->stream));
-    }
-    if (stage == kDenoiseAll) {
-        h->denoiseResult = n == 0 ? 0 : (n - 1) & 1;
-        h->denoiseVarianceValid = false;
-    }
-    return PT_OK;
-}
-
-PT_API int pt_denoise_set_params(pt_handle h, int iterations, float sigma_color, float sigma_plane, int normal_log2_power)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_owner(h)) return rc;
-    if (!std::isfinite(sigma_color) || !std::isfinite(sigma_plane)) return fail(h, PT_E_BAD_ARGUMENT, "sigma_color and sigma_plane must be finite");
-    if (iterations < 0 || iterations > 6 || normal_log2_power < 0 || normal_log2_power > 7 || !(sigma_color > 0.0f) || !(sigma_plane > 0.0f))
-        return fail(h, PT_E_OUT_OF_RANGE, "iterations 0..6, normal_log2_power 0..7, sigma_color > 0, sigma_plane > 0");
-    h->denoiseIterations = iterations; // (read by the next pt_denoise_render; what is queued already took its values)
-    h->denoiseSigmaColor = sigma_color;
-    h->denoiseSigmaPlane = sigma_plane;
-    h->denoiseNormalPower = normal_log2_power;
-    return PT_OK;
-}
-
-PT_API int pt_denoise_set_mode(pt_handle h, int mode, float sigma_variance)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_owner(h)) return rc;
-    if (mode != PT_DENOISE_FIXED && mode != PT_DENOISE_VARIANCE) return fail(h, PT_E_BAD_ARGUMENT, "mode must be PT_DENOISE_FIXED or PT_DENOISE_VARIANCE");
-    if (!std::isfinite(sigma_variance)) return fail(h, PT_E_BAD_ARGUMENT, "sigma_variance must be finite");
-    if (!(sigma_variance > 0.0f)) return fail(h, PT_E_OUT_OF_RANGE, "sigma_variance > 0");
-    h->denoiseMode = mode; // (read by the next pt_denoise_render; what is queued already took its values)
-    h->denoiseSigmaVariance = sigma_variance;
-    return PT_OK;
-}
-
-PT_API int pt_denoise_render(pt_handle h, int guide_frame_index)
-{
-    PT_CHECK_HANDLE(h);
-    if (guide_frame_index < 0) return fail(h, PT_E_BAD_ARGUMENT, "guide_frame_index must be >= 0");
-    if (int rc = denoise_owner(h)) return rc;
-    return denoise_run(h, guide_frame_index, kDenoiseAll);
-}
-
-static int denoise_rendered(pt_handle h)
-{
-    if (int rc = denoise_owner(h)) return rc;
-    if (h->denoiseResult < 0) return fail(h, PT_E_BAD_ARGUMENT, "no pt_denoise_render since the last pt_set_size / pt_set_tile / pt_set_interleaved_tile");
-    return bind_device(h);
-}
-
-static int denoise_copy_out(pt_handle h, void *dst, size_t row_pitch_bytes, const void *src, size_t bytesPerPixel)
-{
-    if (!dst) return fail(h, PT_E_BAD_ARGUMENT, "dst == NULL");
-    const size_t rowBytes = (size_t)h->width * bytesPerPixel;
-    if (row_pitch_bytes == 0) row_pitch_bytes = rowBytes;
-    if (row_pitch_bytes < rowBytes) return fail(h, PT_E_BAD_ARGUMENT, "row pitch smaller than a row");
-    PT_HIP(h, hipMemcpy2DAsync(dst, row_pitch_bytes, src, rowBytes, rowBytes, (size_t)h->rows, hipMemcpyDeviceToHost, h->stream));
-    PT_HIP(h, hipStreamSynchronize(h->stream));
-    return PT_OK;
-}
-
-PT_API int pt_denoise_read(pt_handle h, float *dst, size_t row_pitch_bytes)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_rendered(h)) return rc;
-    return denoise_copy_out(h, dst, row_pitch_bytes, h->dDenoise[h->denoiseResult], 16);
-}
-
-PT_API int pt_denoise_read_guides(pt_handle h, void *dst, size_t row_pitch_bytes)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_rendered(h)) return rc;
-    return denoise_copy_out(h, dst, row_pitch_bytes, h->denoiseIntegratedValid ? h->denoiseSet[h->denoiseCurrent].guides : h->dGuides, 32);
-}
-
-PT_API int pt_denoise_read_variance(pt_handle h, float *dst, size_t row_pitch_bytes)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_rendered(h)) return rc;
-    if (!h->denoiseVarianceValid)
-        return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render made no variance estimate (PT_DENOISE_FIXED, or iterations = 0)");
-    return denoise_copy_out(h, dst, row_pitch_bytes, h->dVariance, 4);
-}
-
-PT_API int pt_denoise_set_temporal(pt_handle h, int enable, int max_history)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_owner(h)) return rc;
-    if (enable != 0 && enable != 1) return fail(h, PT_E_BAD_ARGUMENT, "enable must be 0 or 1");
-    if (max_history < 1 || max_history > 65535) return fail(h, PT_E_OUT_OF_RANGE, "max_history 1..65535");
-    h->denoiseTemporal = enable; // (read by the next pt_denoise_render; what is queued already took its values)
-    h->denoiseMaxHistory = max_history;
-    return PT_OK;
-}
-
-PT_API int pt_denoise_history_clear(pt_handle h)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_owner(h)) return rc;
-    for (pt_renderer::DenoiseSet &set : h->denoiseSet) set.valid = false; // (the buffers stay: a queued render may still read them)
-    h->denoiseHistoryUsed = false;
-    return PT_OK;
-}
-
-PT_API int pt_denoise_read_integrated(pt_handle h, float *dst, size_t row_pitch_bytes)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_rendered(h)) return rc;
-    if (!h->denoiseIntegratedValid) return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render ran with the temporal stage off");
-    return denoise_copy_out(h, dst, row_pitch_bytes, h->denoiseSet[h->denoiseCurrent].image, 16);
-}
-
-PT_API int pt_denoise_read_history(pt_handle h, float *image, void *guides, float out_B[9], float out_O[3])
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_rendered(h)) return rc;
-    if (!h->denoiseHistoryUsed) return fail(h, PT_E_BAD_ARGUMENT, "the last temporal pt_denoise_render had no history");
-    const pt_renderer::DenoiseSet &hist = h->denoiseSet[h->denoiseCurrent ^ 1];
-    if (image)
-        if (int rc = denoise_copy_out(h, image, 0, hist.image, 16)) return rc;
-    if (guides)
-        if (int rc = denoise_copy_out(h, guides, 0, hist.guides, 32)) return rc;
-    if (out_B) std::memcpy(out_B, hist.B, sizeof hist.B);
-    if (out_O) std::memcpy(out_O, hist.O, sizeof hist.O);
-    return PT_OK;
-}
-
-PT_API int pt_denoise_device_ptr(pt_handle h, void **out, size_t *bytes)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_rendered(h)) return rc;
-    if (out) *out = h->dDenoise[h->denoiseResult];
-    if (bytes) *bytes = h->tilePixels() * sizeof(float4);
-    return PT_OK;
-}
-
-PT_API int pt_denoise_present_rgba8(pt_handle h, uint8_t *dst, size_t row_pitch_bytes)
-{
-    PT_CHECK_HANDLE(h);
-    if (int rc = denoise_rendered(h)) return rc;
-    if (!dst) return fail(h, PT_E_BAD_ARGUMENT, "dst == NULL");
-    if (row_pitch_bytes != 0 && row_pitch_bytes < (size_t)h->width * 4) return fail(h, PT_E_BAD_ARGUMENT, "row pitch smaller than a row");
-    if (int rc = join_stripes(h)) return rc; // (dRgba8 is shared with pt_present_rgba8 / pt_postprocess_device: same ordering as theirs)
-    if (int rc = ensure_rgba8(h)) return rc;
-    PT_HIP(h, ptimpl::launch_tone_map(h->presentArithmetic, h->dDenoise[h->denoiseResult], h->dRgba8, h->tilePixels(), h->stream));
-    return denoise_copy_out(h, dst, row_pitch_bytes, h->dRgba8, 4);
-}
-
-// Timing aid (not declared in the public header): one stage of pt_denoise_render on its own — stage -1 = the guide kernel, i >= 0 = pass i
-// of the mode in force, -2 = stage V (the variance estimate; PT_DENOISE_VARIANCE only), -4 = the temporal kernel (pt_denoise_set_temporal
-// on only) — between the buffers a full render uses (a pt_denoise_render must have run, with the temporal switch as it stands now; the
-// result it left is overwritten with a partial one; the sets are neither swapped nor marked).
-extern "C" __attribute__((visibility("default"))) int pt_debug_denoise_stage(pt_handle h, int guide_frame_index, int stage)
-{
-    PT_CHECK_HANDLE(h);
-    if (stage == kDenoiseStageV && (h->denoiseMode != PT_DENOISE_VARIANCE || h->denoiseIterations == 0))
-        return fail(h, PT_E_BAD_ARGUMENT, "stage -2 needs PT_DENOISE_VARIANCE and iterations > 0");
-    if (stage == kDenoiseStageT && !h->denoiseTemporal) return fail(h, PT_E_BAD_ARGUMENT, "stage -4 needs pt_denoise_set_temporal on");
-    if (guide_frame_index < 0 || stage < kDenoiseStageT || stage == kDenoiseAll || stage >= h->denoiseIterations)
-        return fail(h, PT_E_BAD_ARGUMENT, "stage must be -4, -2 .. iterations - 1");
-    if (int rc = denoise_rendered(h)) return rc;
-    if (h->denoiseIntegratedValid != (h->denoiseTemporal != 0))
-        return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render ran with another setting of pt_denoise_set_temporal");
-    return denoise_run(h, guide_frame_index, stage);
 }
 
 // Tuning aid (not declared in the public header): per-wavefront timestamps of the next persistent-kernel launches.

@@ -74,15 +74,37 @@ PT_DEV float dn_u(float r, float g, float b)
     return l / (1.0f + l);
 }
 
-// One pass, one pixel per lane.  S = 1, 2: the step; the 16x16 tile plus a halo of 2 S pixels — G0, G1 and (r, g, b, u) = 48 bytes per
-// pixel — is staged into LDS (S = 2: 24 x 24 x 48 = 27,648 bytes), u evaluated once per staged pixel instead of once per tap.
+// The two guide weights of a tap q for the centre p, shared by the a-trous passes and the temporal stage: wn = max(N_p . N_q, 0) squared
+// normalPower times, wz = max(1 - ((N_p . (P_q - P_p)) / planeDen)^2, 0) with planeDen = sigma_plane * t_p.  Returned apart: each
+// caller multiplies them into its own weight in its own order.
+PT_DEV void dn_guide_weights(const float4 &g0p, const float4 &g1p, const float4 &g0q, const float4 &g1q, float planeDen, int normalPower,
+                             float &wn, float &wz)
+{
+    const float d = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
+    wn = d > 0.0f ? d : 0.0f;
+    for (int k = 0; k < normalPower; k++) wn = wn * wn;
+    const float ex = g0q.x - g0p.x, ey = g0q.y - g0p.y, ez = g0q.z - g0p.z;
+    const float e = (g1p.x * ex + g1p.y * ey) + g1p.z * ez;
+    const float r = e / planeDen;
+    const float z = 1.0f - r * r;
+    wz = z > 0.0f ? z : 0.0f;
+}
+
+// One pass, one pixel per lane, for both modes.  S = 1, 2: the step; the 16x16 tile plus a halo of 2 S pixels — G0, G1 and (r, g, b, u) =
+// 48 bytes per pixel — is staged into LDS (S = 2: 24 x 24 x 48 = 27,648 bytes), u evaluated once per staged pixel instead of once per tap.
 // S = 0: any step (a.step), 64x4 tiles, every tap read from memory — a wavefront is 64 adjacent pixels of one row, so each tap is one
 // coalesced 1 KB load per array; G0 first, G1 and the colour only where the id matches.
-template <int S>
+// VARIANCE (PT_DENOISE_VARIANCE): the luminance stop is scaled by the centre's variance instead of a.invSigma, and the variance is filtered
+// along with the colour (Q += w^2 var_q; output Q / W^2).  The variance of the input travels in colIn's alpha — on pass 0 in a.varIn, the
+// estimate of stage V, since the accumulation image's alpha carries frame tags — and that of the output in colOut's alpha (a.last:
+// alpha = 1).  S = 1, 2: one more float per staged pixel, 52 bytes per pixel, 29,952 bytes at S = 2; S = 0: read with the colour.  The
+// fixed mode has no such array and reads neither a.varIn, a.k2 nor a.last; its alpha is not read and written as 1.
+template <int S, bool VARIANCE>
 __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
 {
     constexpr int TX = S ? 16 : 64, TY = S ? 16 : 4, HALO = 2 * S, LW = TX + 2 * HALO, LH = TY + 2 * HALO;
     __shared__ float4 sG0[S ? LW * LH : 1], sG1[S ? LW * LH : 1], sC[S ? LW * LH : 1];
+    __shared__ float sV[S && VARIANCE ? LW * LH : 1];
     const int tid = threadIdx.x, lx = tid % TX, ly = tid / TX;
     const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
     const int px = x0 + lx, py = y0 + ly;
@@ -93,6 +115,7 @@ __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
             if (qx >= 0 && qx < a.width && qy >= 0 && qy < a.height) { // (cells outside the image are never read: their taps are skipped)
                 const size_t at = (size_t)qy * a.width + qx;
                 float4 c = a.colIn[at];
+                if constexpr (VARIANCE) sV[i] = a.varIn ? a.varIn[at] : c.w;
                 c.w = dn_u(c.x, c.y, c.z);
                 sG0[i] = a.guides[2 * at];
                 sG1[i] = a.guides[2 * at + 1];
@@ -107,12 +130,16 @@ __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
     const float4 g0p = S ? sG0[lc] : a.guides[2 * center];
     const float4 g1p = S ? sG1[lc] : a.guides[2 * center + 1];
     float4 cp = S ? sC[lc] : a.colIn[center];
+    float varp = 1.0f; // (fixed mode: the alpha written)
+    if constexpr (VARIANCE) varp = S ? sV[lc] : (a.varIn ? a.varIn[center] : cp.w);
     const int idp = __float_as_int(g0p.w);
-    float4 out = make_float4(cp.x, cp.y, cp.z, 1.0f);
+    float4 out = make_float4(cp.x, cp.y, cp.z, varp);
     if (idp != -1) {
         const float up = S ? cp.w : dn_u(cp.x, cp.y, cp.z);
         const float planeDen = a.sigmaPlane * g1p.w;
-        float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f;
+        float invp = 0.0f;
+        if constexpr (VARIANCE) invp = 1.0f / (a.k2 * varp + 1e-8f);
+        float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, Q = 0.0f;
 #pragma unroll
         for (int dy = -2; dy <= 2; dy++) {
 #pragma unroll
@@ -128,17 +155,19 @@ __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
                 if (__float_as_int(g0q.w) != idp) continue;
                 const float4 g1q = S ? sG1[lq] : a.guides[2 * at + 1];
                 const float4 cq = S ? sC[lq] : a.colIn[at];
-                const float d = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
-                float wn = d > 0.0f ? d : 0.0f;
-                for (int k = 0; k < a.normalPower; k++) wn = wn * wn;
-                const float ex = g0q.x - g0p.x, ey = g0q.y - g0p.y, ez = g0q.z - g0p.z;
-                const float e = (g1p.x * ex + g1p.y * ey) + g1p.z * ez;
-                const float r = e / planeDen;
-                const float z = 1.0f - r * r;
-                const float wz = z > 0.0f ? z : 0.0f;
+                float varq = 0.0f;
+                if constexpr (VARIANCE) varq = S ? sV[lq] : (a.varIn ? a.varIn[at] : cq.w);
+                float wn, wz;
+                dn_guide_weights(g0p, g1p, g0q, g1q, planeDen, a.normalPower, wn, wz);
                 const float uq = S ? cq.w : dn_u(cq.x, cq.y, cq.z);
-                const float da = (uq - up) * a.invSigma;
-                const float c1 = 1.0f - da * da;
+                float c1;
+                if constexpr (VARIANCE) {
+                    const float du = uq - up;
+                    c1 = 1.0f - (du * du) * invp;
+                } else {
+                    const float da = (uq - up) * a.invSigma;
+                    c1 = 1.0f - da * da;
+                }
                 const float c2 = c1 > 0.0f ? c1 : 0.0f;
                 const float wc = c2 * c2;
                 const float w = ((hk * wn) * wz) * wc;
@@ -146,23 +175,37 @@ __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
                 Sr = Sr + w * cq.x;
                 Sg = Sg + w * cq.y;
                 Sb = Sb + w * cq.z;
+                if constexpr (VARIANCE) Q = Q + (w * w) * varq;
             }
         }
-        if (W > 0.0f) out = make_float4(Sr / W, Sg / W, Sb / W, 1.0f);
+        if (W > 0.0f) out = make_float4(Sr / W, Sg / W, Sb / W, VARIANCE ? Q / (W * W) : 1.0f);
     }
+    if constexpr (VARIANCE)
+        if (a.last) out.w = 1.0f;
     a.colOut[center] = out;
 }
+
+// the mode's instantiation for the step
+template <bool VARIANCE>
+void launch_atrous_steps(const AtrousArgs &a, hipStream_t stream)
+{
+    if (a.step <= 2) {
+        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+        if (a.step == 1) hipLaunchKernelGGL((pt_atrous_kernel<1, VARIANCE>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((pt_atrous_kernel<2, VARIANCE>), grid, dim3(256), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((pt_atrous_kernel<0, VARIANCE>), dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
+    }
+}
+// (the variance mode's three kernels are instantiated behind stage V: pt_variance_kernel<3> stays the sixth function of the file, and the
+// label numbering of its code — which the identity check compares — as it was)
+extern template void launch_atrous_steps<true>(const AtrousArgs &, hipStream_t);
 
 hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream)
 {
     if (a.width < 1 || a.height < 1 || a.step < 1) return hipErrorInvalidValue;
-    if (a.step <= 2) {
-        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-        if (a.step == 1) hipLaunchKernelGGL(pt_atrous_kernel<1>, grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(pt_atrous_kernel<2>, grid, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL(pt_atrous_kernel<0>, dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
-    }
+    if (a.variance) launch_atrous_steps<true>(a, stream);
+    else launch_atrous_steps<false>(a, stream);
     return hipGetLastError();
 }
 
@@ -193,7 +236,7 @@ hipError_t launch_denoise_copy(const float4 *in, float4 *out, size_t n, hipStrea
 // divided out once per staged cell.  Cells outside the image hold an id no guide record has, so "outside" and "another id" are one
 // comparison.  A lane keeps two window rows of 8 cells in registers (64 ds_read_b64 per pixel); Dx and Dy are formed from them and added
 // under selects in the order of the definition (dy outer, dx inner, Dx before Dy).
-// R = 3, the window's radius: a template so that the kernel is emitted behind pt_atrous_kernel<S> and leaves that code as it was.
+// R = 3, the window's radius: a template so that the kernel is emitted behind pt_atrous_kernel<S, false> and leaves that code as it was.
 constexpr int kVarOutsideId = (int)0x80000000;
 
 template <int R>
@@ -258,113 +301,14 @@ hipError_t launch_variance(const VarianceArgs &a, hipStream_t stream)
     return hipGetLastError();
 }
 
-// One variance pass: pt_atrous_kernel<S> with the luminance stop scaled by the centre's variance, and the variance filtered along with the
-// colour (Q += w^2 var_q; output Q / W^2).  The variance of the input travels in colIn's alpha — on pass 0 in a.varIn, the estimate of
-// stage V, since the accumulation image's alpha carries frame tags — and that of the output in colOut's alpha (a.last: alpha = 1).
-// S = 1, 2: the LDS layout of pt_atrous_kernel<S> plus one float per staged pixel for the variance: 52 bytes per pixel, 29,952 bytes at
-// S = 2.  S = 0: direct taps, the variance read with the colour.
-template <int S>
-__global__ __launch_bounds__(256) void pt_atrous_var_kernel(const AtrousVarArgs a)
-{
-    constexpr int TX = S ? 16 : 64, TY = S ? 16 : 4, HALO = 2 * S, LW = TX + 2 * HALO, LH = TY + 2 * HALO;
-    __shared__ float4 sG0[S ? LW * LH : 1], sG1[S ? LW * LH : 1], sC[S ? LW * LH : 1];
-    __shared__ float sV[S ? LW * LH : 1];
-    const int tid = threadIdx.x, lx = tid % TX, ly = tid / TX;
-    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
-    const int px = x0 + lx, py = y0 + ly;
-    const int step = S ? S : a.step;
-    if constexpr (S != 0) {
-        for (int i = tid; i < LW * LH; i += 256) {
-            const int qx = x0 - HALO + i % LW, qy = y0 - HALO + i / LW;
-            if (qx >= 0 && qx < a.width && qy >= 0 && qy < a.height) { // (cells outside the image are never read: their taps are skipped)
-                const size_t at = (size_t)qy * a.width + qx;
-                float4 c = a.colIn[at];
-                sV[i] = a.varIn ? a.varIn[at] : c.w;
-                c.w = dn_u(c.x, c.y, c.z);
-                sG0[i] = a.guides[2 * at];
-                sG1[i] = a.guides[2 * at + 1];
-                sC[i] = c;
-            }
-        }
-        __syncthreads();
-    }
-    if (px >= a.width || py >= a.height) return;
-    const size_t center = (size_t)py * a.width + px;
-    const int lc = (ly + HALO) * LW + lx + HALO;
-    const float4 g0p = S ? sG0[lc] : a.guides[2 * center];
-    const float4 g1p = S ? sG1[lc] : a.guides[2 * center + 1];
-    float4 cp = S ? sC[lc] : a.colIn[center];
-    const float varp = S ? sV[lc] : (a.varIn ? a.varIn[center] : cp.w);
-    const int idp = __float_as_int(g0p.w);
-    float4 out = make_float4(cp.x, cp.y, cp.z, varp);
-    if (idp != -1) {
-        const float up = S ? cp.w : dn_u(cp.x, cp.y, cp.z);
-        const float planeDen = a.sigmaPlane * g1p.w;
-        const float invp = 1.0f / (a.k2 * varp + 1e-8f);
-        float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, Q = 0.0f;
-#pragma unroll
-        for (int dy = -2; dy <= 2; dy++) {
-#pragma unroll
-            for (int dx = -2; dx <= 2; dx++) {
-                const float kx = dx == 0 ? 0.375f : (dx == 1 || dx == -1 ? 0.25f : 0.0625f);
-                const float ky = dy == 0 ? 0.375f : (dy == 1 || dy == -1 ? 0.25f : 0.0625f);
-                const float hk = kx * ky; // (exact)
-                const int qx = px + step * dx, qy = py + step * dy;
-                if (qx < 0 || qx >= a.width || qy < 0 || qy >= a.height) continue;
-                const size_t at = (size_t)qy * a.width + qx;
-                const int lq = lc + dy * S * LW + dx * S;
-                const float4 g0q = S ? sG0[lq] : a.guides[2 * at];
-                if (__float_as_int(g0q.w) != idp) continue;
-                const float4 g1q = S ? sG1[lq] : a.guides[2 * at + 1];
-                const float4 cq = S ? sC[lq] : a.colIn[at];
-                const float varq = S ? sV[lq] : (a.varIn ? a.varIn[at] : cq.w);
-                const float d = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
-                float wn = d > 0.0f ? d : 0.0f;
-                for (int k = 0; k < a.normalPower; k++) wn = wn * wn;
-                const float ex = g0q.x - g0p.x, ey = g0q.y - g0p.y, ez = g0q.z - g0p.z;
-                const float e = (g1p.x * ex + g1p.y * ey) + g1p.z * ez;
-                const float r = e / planeDen;
-                const float z = 1.0f - r * r;
-                const float wz = z > 0.0f ? z : 0.0f;
-                const float uq = S ? cq.w : dn_u(cq.x, cq.y, cq.z);
-                const float du = uq - up;
-                const float a2 = (du * du) * invp;
-                const float c1 = 1.0f - a2;
-                const float c2 = c1 > 0.0f ? c1 : 0.0f;
-                const float wc = c2 * c2;
-                const float w = ((hk * wn) * wz) * wc;
-                W = W + w;
-                Sr = Sr + w * cq.x;
-                Sg = Sg + w * cq.y;
-                Sb = Sb + w * cq.z;
-                Q = Q + (w * w) * varq;
-            }
-        }
-        if (W > 0.0f) out = make_float4(Sr / W, Sg / W, Sb / W, Q / (W * W));
-    }
-    if (a.last) out.w = 1.0f;
-    a.colOut[center] = out;
-}
-
-hipError_t launch_atrous_var(const AtrousVarArgs &a, hipStream_t stream)
-{
-    if (a.width < 1 || a.height < 1 || a.step < 1) return hipErrorInvalidValue;
-    if (a.step <= 2) {
-        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-        if (a.step == 1) hipLaunchKernelGGL(pt_atrous_var_kernel<1>, grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(pt_atrous_var_kernel<2>, grid, dim3(256), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL(pt_atrous_var_kernel<0>, dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
-    }
-    return hipGetLastError();
-}
+template void launch_atrous_steps<true>(const AtrousArgs &, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------- temporal stage (pt_denoise_set_temporal)
 // I(p) = the image's (C, n) blended with the history set's I reprojected to p: the guide position of p goes through the
 // history camera's inverse ray matrix B to a point (fx, fy) of the history image, whose 2x2 neighbours of p's id are weighted by the
-// bilinear weight and the a-trous filter's own normal and plane weights (same expressions, same order), and the weighted mean (colour Hc,
+// bilinear weight and the a-trous filter's own normal and plane weights (dn_guide_weights), and the weighted mean (colour Hc,
 // count m clamped to max_history) is mixed with C by sample counts: I = ((n C + m' Hc) / (n + m'), n + m').  One pixel per lane, 64x4
-// tiles as pt_atrous_kernel<0>: a wavefront is 64 adjacent pixels of one row, so the centre's three 16-byte loads coalesce; the four taps
+// tiles as pt_atrous_kernel<0, *>: a wavefront is 64 adjacent pixels of one row, so the centre's three 16-byte loads coalesce; the four taps
 // are data-dependent gathers — G0 first, G1 and I_h only where the id matches.  Every comparison is false for NaN, so a pixel whose
 // projection is not finite passes through.  fx lies in [-1, W) where taps are formed, so x0 = floor(fx) fits an int and every tap is
 // bounds-checked before its load.
@@ -408,14 +352,8 @@ __global__ __launch_bounds__(256) void pt_temporal_kernel(const TemporalArgs a)
                     const float4 g1q = a.histGuides[2 * at + 1];
                     const float4 hq = a.histImage[at];
                     const float bw = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
-                    const float d = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
-                    float wn = d > 0.0f ? d : 0.0f;
-                    for (int k = 0; k < a.normalPower; k++) wn = wn * wn;
-                    const float ex = g0q.x - g0p.x, ey = g0q.y - g0p.y, ez = g0q.z - g0p.z;
-                    const float e = (g1p.x * ex + g1p.y * ey) + g1p.z * ez;
-                    const float r = e / planeDen;
-                    const float zz = 1.0f - r * r;
-                    const float wz = zz > 0.0f ? zz : 0.0f;
+                    float wn, wz;
+                    dn_guide_weights(g0p, g1p, g0q, g1q, planeDen, a.normalPower, wn, wz);
                     const float w = (bw * wn) * wz;
                     Wh = Wh + w;
                     Sr = Sr + w * hq.x;

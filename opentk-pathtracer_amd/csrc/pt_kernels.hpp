@@ -228,16 +228,23 @@ hipError_t launch_first_hit(const FrameArgs &a, float4 *records, int pickTile, h
 // the preview denoiser (pt_denoise.hip).  Guides: per pixel of the launch (fields as for launch_first_hit) two float4 —
 // (P.xyz, id bits) and (N.xyz, t), id / t as the first-hit record's.
 hipError_t launch_guides(const FrameArgs &a, float4 *guides, hipStream_t stream);
-// one a-trous pass colIn -> colOut over a width x height image (compact rows); colIn's alpha is not read, colOut's is 1
+// one a-trous pass colIn -> colOut over a width x height image (compact rows).  Fixed mode (variance = 0): colIn's alpha is not read,
+// colOut's is 1; varIn, k2 and last are not read.  Variance-guided mode (PT_DENOISE_VARIANCE; variance = 1): the variance of the input is
+// varIn (pass 0: stage V's buffer) or, where varIn is null, colIn's alpha; that of the output is colOut's alpha, or alpha = 1 on the last
+// pass; invSigma is not read
 struct AtrousArgs {
     const float4 *colIn;
+    const float *varIn;
     const float4 *guides;
     float4 *colOut;
     int width, height;
     int step;         // 2^i for pass i
+    int variance;     // the mode: 0 = the luminance stop is invSigma's, 1 = it is scaled by k2 times the centre's variance
     float invSigma;   // 1.0f / (sigma_color * 2^-i), computed by the host in binary32
+    float k2;         // sigma_variance * sigma_variance, computed by the host in binary32
     float sigmaPlane;
     int normalPower;  // the normal weight is squared this many times
+    int last;         // the last pass writes alpha 1
 };
 hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream);
 hipError_t launch_denoise_copy(const float4 *in, float4 *out, size_t pixels, hipStream_t stream); // out = (in.rgb, 1)
@@ -249,21 +256,6 @@ struct VarianceArgs {
     int width, height;
 };
 hipError_t launch_variance(const VarianceArgs &a, hipStream_t stream);
-// one variance pass colIn -> colOut: the variance of the input is varIn (pass 0: stage V's buffer) or, where varIn is null, colIn's alpha;
-// that of the output is colOut's alpha, or alpha = 1 on the last pass
-struct AtrousVarArgs {
-    const float4 *colIn;
-    const float *varIn;
-    const float4 *guides;
-    float4 *colOut;
-    int width, height;
-    int step;         // 2^i for pass i
-    float k2;         // sigma_variance * sigma_variance, computed by the host in binary32
-    float sigmaPlane;
-    int normalPower;  // the normal weight is squared this many times
-    int last;         // the last pass writes alpha 1
-};
-hipError_t launch_atrous_var(const AtrousVarArgs &a, hipStream_t stream);
 // the temporal stage (pt_denoise_set_temporal): out = (colIn.rgb, n) blended per pixel with the history image reprojected through the
 // guides' world positions and the history's camera; out's alpha = the pixel's sample count.  histImage == null: no valid history
 struct TemporalArgs {

@@ -1,5 +1,6 @@
-// pt_renderer.hpp — host-side state behind a pt_handle, shared by mi355pt.cpp (one renderer on one GPU) and
-// mi355pt_multi.cpp (a group of renderers, one per GPU, row-tiled; gather over xGMI at read / present time).
+// pt_renderer.hpp — host-side state behind a pt_handle, shared by mi355pt.cpp (one renderer on one GPU), mi355pt_queries.cpp (its
+// first-hit query and preview denoiser) and mi355pt_multi.cpp (a group of renderers, one per GPU, row-tiled; gather over xGMI at read /
+// present time).
 //
 // What the reference keeps in the C# class PathTracer (/root/reference/OpenTK-PathTracer/src/Render/PathTracer.cs:9-141)
 // plus the two UBOs MainWindow owns (src/MainWindow.cs:195-201), and the HIP plumbing around the kernels of
@@ -168,37 +169,65 @@ struct pt_renderer {
     // since.  dPick: the 64 records of the one tile a pt_pick traces.
     float4 *dFirstHit = nullptr;
     float4 *dPick = nullptr;
-    // Preview denoiser (pt_denoise_render, pt_denoise.hip): rows x width guide records of 32 bytes and the two ping-pong images of the
-    // a-trous passes, allocated by the first pt_denoise_render after a (re)size or (re)tiling and freed by the next one — never on the
-    // pt_render path.  denoiseResult: which of the two images holds the last result (-1 = nothing rendered since).
-    float4 *dGuides = nullptr;
-    float4 *dDenoise[2] = {nullptr, nullptr};
-    int denoiseResult = -1;
-    int denoiseIterations = 5, denoiseNormalPower = 5; // pt_denoise_set_params
-    float denoiseSigmaColor = 0.5f, denoiseSigmaPlane = 0.02f;
-    // Variance-guided mode (pt_denoise_set_mode): dVariance = stage V's estimate V0, rows x width floats, allocated by the first
-    // pt_denoise_render in that mode and freed with the buffers above; denoiseVarianceValid: the last pt_denoise_render made one.
-    int denoiseMode = 0; // PT_DENOISE_FIXED
-    float denoiseSigmaVariance = 6.0f;
-    float *dVariance = nullptr;
-    bool denoiseVarianceValid = false;
-    // Temporal stage (pt_denoise_set_temporal).  A set = one integrated image (rgb, count), one guide buffer (beside dGuides, which the
-    // renders with the stage off keep to themselves), the camera it was made under (B = the inverse of the ray matrix, O = the ray
-    // origin), the reset epoch it was made in and a valid flag.  denoiseSet[denoiseCurrent] is the current set, the other one the
-    // history; both allocated by the first temporal pt_denoise_render after a (re)size or (re)tiling and freed with the buffers above —
-    // never on the pt_render path.  resetEpoch: bumped by pt_reset, pt_write_result, pt_set_size, pt_set_tile, pt_set_interleaved_tile.
+    // Temporal stage of the denoiser (pt_denoise_set_temporal).  A set = one integrated image (rgb, count), one guide buffer (beside dGuides,
+    // which the renders with the stage off keep to themselves), the camera it was made under (B = the inverse of the ray matrix, O = the
+    // ray origin), the reset epoch it was made in and a valid flag.
     struct DenoiseSet {
         float4 *image = nullptr, *guides = nullptr;
         float B[9] = {0}, O[3] = {0};
         unsigned long long epoch = 0;
         bool valid = false;
     };
-    DenoiseSet denoiseSet[2];
-    int denoiseCurrent = 0;
+    struct Denoiser {
+        // Preview denoiser (pt_denoise_render, pt_denoise.hip): rows x width guide records of 32 bytes and the two ping-pong images of the
+        // a-trous passes, allocated by the first pt_denoise_render after a (re)size or (re)tiling and freed by the next one — never on the
+        // pt_render path.  result: which of the two images holds the last result (-1 = nothing rendered since).
+        float4 *dGuides = nullptr;
+        float4 *dImage[2] = {nullptr, nullptr};
+        int result = -1;
+        int iterations = 5, normalPower = 5; // pt_denoise_set_params
+        float sigmaColor = 0.5f, sigmaPlane = 0.02f;
+        // Variance-guided mode (pt_denoise_set_mode): dVariance = stage V's estimate V0, rows x width floats, allocated by the first
+        // pt_denoise_render in that mode and freed with the buffers above; varianceValid: the last pt_denoise_render made one.
+        int mode = 0; // PT_DENOISE_FIXED
+        float sigmaVariance = 6.0f;
+        float *dVariance = nullptr;
+        bool varianceValid = false;
+        // Temporal stage: set[current] is the current set, the other one the history; both allocated by the first temporal
+        // pt_denoise_render after a (re)size or (re)tiling and freed with the buffers above — never on the pt_render path.
+        DenoiseSet set[2];
+        int current = 0;
+        int temporal = 0, maxHistory = 32;
+        bool integratedValid = false; // the last pt_denoise_render ran with the stage on (its I and guides are the current set's) ...
+        bool historyUsed = false;     // ... and read a valid history set
+
+        bool allocated() const
+        {
+            return dGuides || dImage[0] || dImage[1] || dVariance || set[0].image || set[0].guides || set[1].image || set[1].guides;
+        }
+        // frees whatever is allocated and nulls the pointers (the caller has made sure that nothing queued still uses them); the first error
+        hipError_t release()
+        {
+            hipError_t first = hipSuccess;
+            auto drop = [&first](auto *&p) {
+                if (p) {
+                    const hipError_t e = hipFree(p);
+                    if (first == hipSuccess) first = e;
+                }
+                p = nullptr;
+            };
+            drop(dGuides);
+            drop(dVariance);
+            for (float4 *&img : dImage) drop(img);
+            for (DenoiseSet &s : set) {
+                drop(s.image);
+                drop(s.guides);
+            }
+            return first;
+        }
+    } denoise;
+    // bumped by pt_reset, pt_write_result, pt_set_size, pt_set_tile, pt_set_interleaved_tile: a denoiser set of an earlier epoch is history
     unsigned long long resetEpoch = 0;
-    int denoiseTemporal = 0, denoiseMaxHistory = 32;
-    bool denoiseIntegratedValid = false; // the last pt_denoise_render ran with the stage on (its I and guides are the current set's) ...
-    bool denoiseHistoryUsed = false;     // ... and read a valid history set
 
     // hand-over audit (only allocated by the -DPT_AUDIT build, see pt_debug_hooks.hpp): side word per accumulation pixel + violation log
     unsigned long long *dAudit = nullptr;
@@ -310,6 +339,18 @@ int hip_fail(pt_handle h, hipError_t e, const char *what);
         if (e_ != hipSuccess) return ptimpl::hip_fail((h), e_, #call);                                                 \
     } while (0)
 
+// group handles: replicate a call to every part; the first failure is reported on the group handle
+#define PT_FAN_OUT(h, call)                                                                                            \
+    do {                                                                                                               \
+        if ((h)->isGroup()) {                                                                                          \
+            for (pt_handle part : (h)->parts) {                                                                        \
+                int rc_ = (call);                                                                                      \
+                if (rc_ != PT_OK) return ptimpl::fail((h), rc_, part->error);                                                  \
+            }                                                                                                          \
+            return PT_OK;                                                                                              \
+        }                                                                                                              \
+    } while (0)
+
 int bind_device(pt_handle h);
 void feed_close(pt_handle h);   // the open frame-fed launch (if any) takes no more frames; bookkeeping of its final frame count
 int flush_frames(pt_handle h);  // launch the frames pt_render deferred (a blocking entry point's flush: may wait chain_wait_us per launch)
@@ -325,6 +366,7 @@ hipEvent_t next_launch_event(pt_handle h);
 int fix_alpha(pt_handle h, bool repairNow = true); // join + restore alpha = 1 if the image still carries frame tags (before the host observes it)
 int ensure_stripe(pt_handle h, int j); // create stripe stream j (j > 0) and its event on first use
 hipStream_t stripe_stream(pt_handle h, int j); // stripe 0 runs on the main stream
+int ensure_rgba8(pt_handle h); // h->dRgba8 holds this handle's rows
 // tone map this handle's rows into `dst` (RGBA8, compact rows) on h->stream, behind every frame rendered so far
 int tone_map_into(pt_handle h, void *dst);
 // the tone-map pass of a present in the given arithmetic (pt_present_set_arithmetic); every present path launches it through here

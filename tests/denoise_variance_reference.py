@@ -5,7 +5,7 @@ The conventions are those of denoise_reference.py, which this file builds on and
 operation on float32 arrays, in the order the definition gives, nothing fused, selects are np.where (NaN > 0 is False), one vectorised
 shift per tap, accumulated in tap order (dy outer, dx inner).  u, the guides, the taps, the kernel h, the id rule, w_n and w_z are
 denoise_reference's; only the luminance stop differs, and the variance it is scaled by is estimated (stage V) and filtered here.
-csrc/pt_denoise.hip (pt_variance_kernel, pt_atrous_var_kernel) must reproduce this bit for bit (tests/test_gpu_denoise_variance.py);
+csrc/pt_denoise.hip (pt_variance_kernel, pt_atrous_kernel<S, true>) must reproduce this bit for bit (tests/test_gpu_denoise_variance.py);
 tests/test_denoise_variance_cpu.py checks the properties of the restatement itself.
 """
 from __future__ import annotations

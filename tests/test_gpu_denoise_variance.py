@@ -1,5 +1,5 @@
 """The variance-guided mode of the preview denoiser on the GPU (pt_denoise_set_mode / pt_denoise_read_variance; pt_variance_kernel and
-pt_atrous_var_kernel in csrc/pt_denoise.hip) against its definition: the estimate and the passes equal the numpy float32 restatement
+pt_atrous_kernel<S, true> in csrc/pt_denoise.hip) against its definition: the estimate and the passes equal the numpy float32 restatement
 (tests/denoise_variance_reference.py; its own properties: tests/test_denoise_variance_cpu.py) on the GPU's own image and guides on every
 pixel, bit for bit; the fixed mode and pt_render do not notice; the argument checks; quality against the fixed mode (asserted) and cost
 (measured), both recorded in DESIGN.md 3.5."""
@@ -48,6 +48,7 @@ CASES = [
     VCase("empty_16x9", BY["empty_16x9"], 1),          # no objects: output == input, V0 = 0
     VCase("iterations0", BY["default_75x43_f0"], 1, dr.Params(iterations=0)),  # a copy; pt_denoise_read_variance is refused
     VCase("iterations1", BY["default_75x43_f0"], 1, dr.Params(iterations=1)),  # the first pass is the last: V0 buffer in, alpha 1 out
+    VCase("iterations2", BY["default_75x43_f0"], 1, dr.Params(iterations=2)),  # the last pass is the step-2 instantiation
     VCase("iterations6", _default(131, 67), 1, dr.Params(iterations=6)),
     VCase("sigma3_plane_power", BY["default_75x43_f0"], 2, dr.Params(iterations=4, sigma_plane=0.05, normal_log2_power=2), 3.0),
     VCase("sigma8_plane_power", BY["default_75x43_ap0"], 1, dr.Params(iterations=3, sigma_plane=0.004, normal_log2_power=7), 8.0),
