@@ -26,13 +26,15 @@ class Params:
 
 def inv_sigma(sigma_color: float, i: int) -> np.float32:
     """1.0f / (sigma_color * 2^-i) in binary32, as the host computes the kernel argument of pass i."""
-    return F(1.0) / (F(sigma_color) * F(2.0 ** -i))
+    with np.errstate(all="ignore"):  # (a subnormal sigma_color gives inf, by IEEE and without a warning)
+        return F(1.0) / (F(sigma_color) * F(2.0 ** -i))
 
 
 def u_of(c: np.ndarray) -> np.ndarray:
     """u = l / (1 + l), l = 0.2126 r + 0.7152 g + 0.0722 b evaluated left to right."""
-    l = (F(0.2126) * c[..., 0] + F(0.7152) * c[..., 1]) + F(0.0722) * c[..., 2]
-    return l / (F(1.0) + l)
+    with np.errstate(all="ignore"):  # (l may overflow, 1 + l may be 0: the quotient is what IEEE says, and no warning is wanted)
+        l = (F(0.2126) * c[..., 0] + F(0.7152) * c[..., 1]) + F(0.0722) * c[..., 2]
+        return l / (F(1.0) + l)
 
 
 def _dot(a, b):
@@ -47,7 +49,8 @@ def atrous_pass(colour: np.ndarray, guides: np.ndarray, i: int, p: Params) -> np
     ids, pos, nrm, t = guides["id"], guides["pos"], guides["normal"], guides["t"]
     u = u_of(rgb)
     isig = inv_sigma(p.sigma_color, i)
-    den = F(p.sigma_plane) * t
+    with np.errstate(all="ignore"):  # (sigma_plane near FLT_MAX: the product is inf, by IEEE and without a warning)
+        den = F(p.sigma_plane) * t
     Wsum = np.zeros((H, W), F)
     S = np.zeros((H, W, 3), F)
     with np.errstate(all="ignore"):

@@ -21,7 +21,8 @@ DEFAULT_SIGMA_VARIANCE = 6.0
 
 def k2_of(sigma_variance: float) -> np.float32:
     """sigma_variance * sigma_variance in binary32, as the host computes the kernel argument."""
-    return F(sigma_variance) * F(sigma_variance)
+    with np.errstate(all="ignore"):  # (the square may overflow to inf or underflow to 0, by IEEE and without a warning)
+        return F(sigma_variance) * F(sigma_variance)
 
 
 def _shift(H, W, oy, ox):
@@ -77,7 +78,8 @@ def variance_pass(colour: np.ndarray, var: np.ndarray, guides: np.ndarray, i: in
     ids, pos, nrm, t = guides["id"], guides["pos"], guides["normal"], guides["t"]
     u = dr.u_of(rgb)
     k2 = k2_of(sigma_variance)
-    den = F(p.sigma_plane) * t
+    with np.errstate(all="ignore"):  # (sigma_plane near FLT_MAX: the product is inf, by IEEE and without a warning)
+        den = F(p.sigma_plane) * t
     Wsum = np.zeros((H, W), F)
     S = np.zeros((H, W, 3), F)
     Qsum = np.zeros((H, W), F)
