@@ -889,7 +889,14 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
         if constexpr (FEED) {
             if (am != 0ull) idleSince = 0u; // (the idle clock runs only while the wavefront has nothing to trace)
         }
+        // An iteration with nothing to trace does not jump back to the top of the loop: it goes THROUGH the bounce region with every lane
+        // switched off (idleIter: its own housekeeping is skipped).  A `continue` here made the path state undefined on this way round the
+        // bounce, and a state that is undefined on one way and live on the other cannot share its registers with the state the bounce
+        // leaves behind: the compiler kept two register sets and copied one to the other three times per iteration (docs/kernels.md,
+        // "Path state in place").
+        bool idleIter = false;
         if (am == 0ull) {
+            idleIter = true;
             if (parking && nparked > 0) { // nothing to trace: look after the parked resolves (they must be gone before leaving)
                 service_parked();
                 if (nparked > 0) {
@@ -949,22 +956,24 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
                     continue;
                 }
             }
-            if (!(exhausted && avail == 0 && nparked == 0)) continue;
-            if (!compaction) break;
-            // ---- leaving: the last wavefront of the workgroup must outlive every donor and empty the pool
-            unsigned int old = 0;
-            if (leader) old = atomicSub(&drain.alive, 1u);
-            old = (unsigned int)__builtin_amdgcn_readfirstlane((int)old);
-            if (old > 1u) break;
-            lastAlive = true;
-            unsigned int pushing = lds_load(&drain.pushing), pushed = lds_load(&drain.pushed), taken = lds_load(&drain.taken);
-            bool pending = __builtin_amdgcn_readfirstlane((int)(pushing != 0u || pushed != taken)) != 0;
-            if (!pending) break;
-            if (leader) atomicAdd(&drain.alive, 1u);
-            __builtin_amdgcn_s_sleep(1);
-            continue;
+            if (exhausted && avail == 0 && nparked == 0) {
+                if (!compaction) break;
+                // ---- leaving: the last wavefront of the workgroup must outlive every donor and empty the pool
+                unsigned int old = 0;
+                if (leader) old = atomicSub(&drain.alive, 1u);
+                old = (unsigned int)__builtin_amdgcn_readfirstlane((int)old);
+                if (old > 1u) break;
+                lastAlive = true;
+                unsigned int pushing = lds_load(&drain.pushing), pushed = lds_load(&drain.pushed), taken = lds_load(&drain.taken);
+                bool pending = __builtin_amdgcn_readfirstlane((int)(pushing != 0u || pushed != taken)) != 0;
+                if (!pending) break;
+                if (leader) atomicAdd(&drain.alive, 1u);
+                __builtin_amdgcn_s_sleep(1);
+                continue;
+            }
+            if constexpr (!SPP1) continue; // (the multi-sample rows keep their state in more registers than a second set costs them: as before)
         }
-        if (compaction && exhausted && avail == 0 && !lastAlive && __builtin_popcountll(am) <= donateMax) {
+        if (!idleIter && compaction && exhausted && avail == 0 && !lastAlive && __builtin_popcountll(am) <= donateMax) {
             // ---- donate: commit (pushing++, alive--), publish the live paths under the donor lock, exit
             unsigned int old = 0, base = 0;
             if (leader) {
@@ -1017,11 +1026,11 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
                 atomicSub(&drain.pushing, 1u);
             }
         }
-        if (TIMELINE) nIter++;
+        if (TIMELINE && !idleIter) nIter++;
         PROF_MARK(0) // feed: ring refill / pop / adopt / donate
 #ifdef PT_PROFILE
         // lane utilisation of the generic bounce iteration: iterations, active lanes, lanes waiting for their pixel
-        prof_util[0] += 1ull;
+        prof_util[0] += idleIter ? 0ull : 1ull;
         prof_util[1] += (unsigned long long)__builtin_popcountll(am);
         prof_util[2] += (unsigned long long)__builtin_popcountll(__ballot(active && pending));
 #endif
@@ -1030,7 +1039,12 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
             // front of every level of a nest whose inside modifies it)
             const bool trace = active && !pending;
             bool cont = false;
-            if (trace && bounce < a.rayDepth) cont = bounce_step_t<false, MATLDS, GRID, (MATLDS && !GRID)>(sc, a.numSpheres, a.numCuboids, env, ro, rd, throughput, rad, seed, nullptr, walkFrom PROF_PASS);
+            // The object counts are made opaque here, once per iteration: what the traversal asks about them ("any four-sphere step", "a
+            // sphere left over", "an odd cuboid") is then a scalar compare at the use.  Hoisted out of the loop, each answer was a 64-bit
+            // lane mask that did not fit the scalar registers and came back through two v_readlane per iteration.
+            int nsIter = a.numSpheres, ncIter = a.numCuboids;
+            asm volatile("" : "+s"(nsIter), "+s"(ncIter));
+            if (trace && bounce < a.rayDepth) cont = bounce_step_t<false, MATLDS, GRID, (MATLDS && !GRID)>(sc, nsIter, ncIter, env, ro, rd, throughput, rad, seed, nullptr, walkFrom PROF_PASS);
             if (trace && !(GRID && walkFrom >= 0.0f)) { // (else: the grid walk of this bounce continues in the next iteration, pt_device.hpp WALK SLICES)
                 bounce++;
                 pending = !cont || bounce >= a.rayDepth;
@@ -1050,7 +1064,7 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
                     pending = false;
                 }
             }
-            if (parking) {
+            if (parking && !idleIter) {
                 // a resolve that has to wait gives its lane back: the result is parked, the wavefront's first lanes retry it
                 const bool wait = pix >= 0 && pending;
                 if (park_resolves(wait, pix, fj, v_add(V(0.0f, 0.0f, 0.0f), rad))) {
@@ -1062,7 +1076,7 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
             // results that wait for their pixel's previous frame (in their lanes, or parked): the wall-clock bound; an abandoned launch drops them
             const bool waits = pix >= 0 && pending;
             const unsigned long long waitMask = __ballot(waits);
-            if (waitMask != 0ull || nparked > 0) {
+            if (!idleIter && (waitMask != 0ull || nparked > 0)) {
                 if (bound.tick(waitMask, parkSince, nparked > 0 && !parkProgress)) {
                     if (waits) {
                         pix = -1;
