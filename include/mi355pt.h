@@ -307,7 +307,21 @@ PT_API int pt_present_set_arithmetic(pt_handle h, int mode);
  *   words 0-2 ray origin; word 3 t = the T RayTrace leaves (the smallest positive root: the EXIT distance when the origin lies inside
  *   the winner), +inf on a miss; words 4-6 ray direction; word 7 id as int32 bits: -1 miss, i = sphere i, PT_MAX_SPHERES + j = cuboid j.
  * Read: the current camera blob, scene blob and parameters.  Neither read nor written: the accumulation image, the frame counter, the
- * environment (none is needed), the three arithmetic switches. */
+ * environment (none is needed), the three arithmetic switches.
+ * With aperture > 0 that ray is one lens sample: near an out-of-focus silhouette the answer changes with frame_index.  That holds for
+ * the default, PT_RAY_SAMPLE0, only: under PT_RAY_PINHOLE (pt_first_hit_set_ray) the record describes a stable ray, whatever the lens. */
+
+/* Which ray the records describe (pt_first_hit_set_ray).  SAMPLE0: sample 0 of frame frame_index, as above.  PINHOLE: the pinhole ray
+ * through the pixel's centre — what MainWindow.cs:302-318 aims at, a stable ray through the cursor, traced with the shader's own
+ * RayTrace: the NDC point of compute.glsl:113-115 with both sub-pixel draws replaced by 0.5, GetWorldSpaceRay (:352-357), normalised;
+ * origin = InvView's translation column (the origin of :120 at aperture 0, bit for bit); no lens, no RNG draw: frame_index, focal length
+ * and aperture do not enter the result. */
+enum { PT_RAY_SAMPLE0 = 0, PT_RAY_PINHOLE = 1 };
+/* The ray of the pt_first_hit_render and pt_pick calls that follow (the click of Gui.cs:223-233 -> MainWindow.cs:302-318); what is
+ * queued already keeps the ray it was issued under.  Default PT_RAY_SAMPLE0.  The record layout does not change, frame_index is still
+ * validated, and nothing is read or written that the query did not touch before.  Any other mode: PT_E_BAD_ARGUMENT, and the previous
+ * mode stays in force.  Works under pt_set_tile / pt_set_interleaved_tile; group handles: every device takes the mode. */
+PT_API int pt_first_hit_set_ray(pt_handle h, int mode);
 
 /* Gui.cs:223-233 / MainWindow.cs:302-318 for EVERY pixel of this handle's rows (an id / depth image for an outline or denoising
  * pass): stream-ordered and asynchronous; launches what is pending first.  The rows x width x 32-byte device buffer is allocated by
@@ -342,7 +356,8 @@ PT_API int pt_pick(pt_handle h, int x, int y, int frame_index, int *out_id, floa
  * The definition, operation by operation (it is reproducible bit for bit in binary32), is DESIGN.md section 3.5.
  * SCOPE: single-GPU handles that own the whole image.  A group handle, or a handle under pt_set_tile (other than all rows) /
  * pt_set_interleaved_tile, gets PT_E_BAD_ARGUMENT from all of these calls: the filter reads up to 62 rows beyond a pixel's own.  With
- * aperture > 0 the guides are lens-jittered like the first-hit record: the filter is specified, but only sharp at aperture 0. */
+ * aperture > 0 and the default switches the guides are lens-jittered like the first-hit record of PT_RAY_SAMPLE0: the filter is
+ * specified, but its guides describe one lens sample of a pixel that shows the mean of many.  pt_denoise_set_lens is for that case. */
 
 /* Filter parameters of the pt_denoise_render calls that follow — a GUI slider's setter, like those MainWindow.cs:49-63 drives; the result
  * is shown through ScreenEffect.cs:29-37.  iterations 0..6 (0 = the image is copied), sigma_color > 0 (luminance edge-stop; halves every
@@ -424,6 +439,21 @@ PT_API int pt_denoise_read_integrated(pt_handle h, float *dst, size_t row_pitch_
  * out_B (P - out_O) = lambda (ndc x, ndc y, 1) for a point P seen by that camera.  Every pointer may be NULL.  PT_E_BAD_ARGUMENT when
  * that render had no history (or none was made since the last (re)size / (re)tiling / pt_denoise_history_clear). */
 PT_API int pt_denoise_read_history(pt_handle h, float *image, void *guides, float out_B[9], float out_O[3]);
+
+/* Lens mode of the pt_denoise_render calls that follow, for a host that renders with the lens open (the reference's own start:
+ * new PathTracer(env, W, H, 13, 1, 20f, 0.14f), MainWindow.cs:189, shown through MainWindow.cs:49-63 / ScreenEffect.cs:29-37); what is
+ * queued already keeps the values it was issued under.  enable = 1 changes two things.  (a) The guide records
+ * come from the pinhole ray of PT_RAY_PINHOLE instead of sample 0 — same 32 bytes, same fields, the same rules; guide_frame_index is
+ * validated and does not enter; stage V, the temporal stage and its sets consume them unchanged, and the temporal reprojection, which
+ * always went through a pinhole camera, now meets guides of that camera.  (b) Every pixel gets a blur radius in pixels from its guide t,
+ * c = (cocK |t - F|) / t, c = cocK on a miss, where cocK = coc_scale (A / 2) / F H / (2 |InvProjection[5]|) with the handle's aperture
+ * A, focal length F and image height H (0 when A <= 0, F <= 0 or not finite).  A tap at Chebyshev distance r = step max(|dx|, |dy|)
+ * from its centre p with r <= c(p) and r <= c(q) lies inside what the lens has already blurred at both ends: its id is not compared
+ * and its normal and plane weights are 1; the luminance stop of the mode in force still applies.  Every other tap follows the rules
+ * above, and a miss pixel still passes through.  coc_scale = 0: pinhole guides under the old tap rules.
+ * enable other than 0 or 1, or a non-finite coc_scale: PT_E_BAD_ARGUMENT; coc_scale < 0: PT_E_OUT_OF_RANGE; the previous values stay in
+ * force then.  Defaults 0, 1.  With enable = 0 pt_denoise_render is bit for bit what it was.  Scope as for pt_denoise_set_params. */
+PT_API int pt_denoise_set_lens(pt_handle h, int enable, float coc_scale);
 
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);

@@ -73,6 +73,15 @@ static void first_hit_args(pt_handle h, pt::FrameArgs &a, int frame_index)
     a.tilesY = (h->rows + 7) / 8;
 }
 
+PT_API int pt_first_hit_set_ray(pt_handle h, int mode)
+{
+    PT_CHECK_HANDLE(h);
+    if (mode != PT_RAY_SAMPLE0 && mode != PT_RAY_PINHOLE) return fail(h, PT_E_BAD_ARGUMENT, "mode must be PT_RAY_SAMPLE0 or PT_RAY_PINHOLE");
+    PT_FAN_OUT(h, pt_first_hit_set_ray(part, mode));
+    h->firstHitRay = mode; // (read by the next pt_first_hit_render / pt_pick; what is queued already took its value)
+    return PT_OK;
+}
+
 PT_API int pt_first_hit_render(pt_handle h, int frame_index)
 {
     PT_CHECK_HANDLE(h);
@@ -83,7 +92,7 @@ PT_API int pt_first_hit_render(pt_handle h, int frame_index)
     if (!h->dFirstHit) PT_HIP(h, hipMalloc((void **)&h->dFirstHit, h->tilePixels() * 2 * sizeof(float4)));
     pt::FrameArgs a;
     first_hit_args(h, a, frame_index);
-    PT_HIP(h, pt::launch_first_hit(a, h->dFirstHit, -1, h->stream));
+    PT_HIP(h, pt::launch_first_hit(a, h->dFirstHit, -1, h->firstHitRay == PT_RAY_PINHOLE, h->stream));
     return PT_OK;
 }
 
@@ -133,7 +142,7 @@ PT_API int pt_pick(pt_handle h, int x, int y, int frame_index, int *out_id, floa
     if (!h->dPick) PT_HIP(h, hipMalloc((void **)&h->dPick, 64 * 2 * sizeof(float4)));
     pt::FrameArgs a;
     first_hit_args(h, a, frame_index);
-    PT_HIP(h, pt::launch_first_hit(a, h->dPick, (ly >> 3) * a.tilesX + (x >> 3), h->stream));
+    PT_HIP(h, pt::launch_first_hit(a, h->dPick, (ly >> 3) * a.tilesX + (x >> 3), h->firstHitRay == PT_RAY_PINHOLE, h->stream));
     float rec[8];
     PT_HIP(h, hipMemcpyAsync(rec, h->dPick + 2 * ((ly & 7) * 8 + (x & 7)), sizeof rec, hipMemcpyDeviceToHost, h->stream));
     PT_HIP(h, hipStreamSynchronize(h->stream));
@@ -187,6 +196,18 @@ static bool denoise_set_camera(const unsigned char *basic, float B[9], float O[3
     return ok;
 }
 
+// The blur radius per unit of |t - F| / t, in pixels at the image centre: coc_scale (A / 2) / F H / (2 |invProj[5]|) in
+// double from the binary32 inputs, rounded once; 0 = no tap is relaxed (no lens, coc_scale 0, or not finite).
+static float denoise_coc_k(pt_handle h)
+{
+    float m5;
+    std::memcpy(&m5, h->basic + 5 * sizeof(float), sizeof m5);
+    const double A = h->apertureDiameter, F = h->focalLength, s = h->denoise.cocScale;
+    if (!(A > 0.0) || !(F > 0.0) || s == 0.0) return 0.0f;
+    const float k = (float)(s * (A / 2.0) / F * (double)h->height / (2.0 * std::fabs((double)m5)));
+    return std::isfinite(k) ? k : 0.0f;
+}
+
 // stage kDenoiseAll: everything; -1: the guides only; kDenoiseStageV: stage V of the variance mode only; kDenoiseStageT: the temporal
 // kernel only; i >= 0: pass i only (pt_debug_denoise_stage, for timing)
 constexpr int kDenoiseStageV = -2, kDenoiseAll = -3, kDenoiseStageT = -4;
@@ -199,6 +220,8 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
     const size_t pixels = h->tilePixels();
     const bool variance = d.mode == PT_DENOISE_VARIANCE;
     const bool temporal = d.temporal != 0;
+    const bool lens = d.lens != 0;
+    const float cocK = lens ? denoise_coc_k(h) : 0.0f;
     if (!temporal && !d.dGuides) PT_HIP(h, hipMalloc((void **)&d.dGuides, pixels * 2 * sizeof(float4)));
     for (float4 *&img : d.dImage)
         if (!img) PT_HIP(h, hipMalloc((void **)&img, pixels * sizeof(float4)));
@@ -221,7 +244,7 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
     if (stage == kDenoiseAll || stage == -1) {
         pt::FrameArgs a;
         first_hit_args(h, a, guide_frame_index);
-        PT_HIP(h, pt::launch_guides(a, guides, h->stream));
+        PT_HIP(h, pt::launch_guides(a, guides, lens, h->stream));
         if (stage == -1) return PT_OK;
     }
     if (temporal && (stage == kDenoiseAll || stage == kDenoiseStageT)) {
@@ -274,6 +297,9 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
         t.k2 = variance ? d.sigmaVariance * d.sigmaVariance : 0.0f;
         t.varIn = variance && i == 0 ? d.dVariance : nullptr;
         t.last = variance && i == n - 1;
+        t.lens = cocK > 0.0f; // (lens mode with cocK = 0: the pinhole guides under the tap rules of lens = 0)
+        t.cocK = cocK;
+        t.focal = h->focalLength;
         PT_HIP(h, pt::launch_atrous(t, h->stream));
     }
     if (stage == kDenoiseAll) {
@@ -306,6 +332,18 @@ PT_API int pt_denoise_set_mode(pt_handle h, int mode, float sigma_variance)
     if (!(sigma_variance > 0.0f)) return fail(h, PT_E_OUT_OF_RANGE, "sigma_variance > 0");
     h->denoise.mode = mode; // (read by the next pt_denoise_render; what is queued already took its values)
     h->denoise.sigmaVariance = sigma_variance;
+    return PT_OK;
+}
+
+PT_API int pt_denoise_set_lens(pt_handle h, int enable, float coc_scale)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    if (enable != 0 && enable != 1) return fail(h, PT_E_BAD_ARGUMENT, "enable must be 0 or 1");
+    if (!std::isfinite(coc_scale)) return fail(h, PT_E_BAD_ARGUMENT, "coc_scale must be finite");
+    if (coc_scale < 0.0f) return fail(h, PT_E_OUT_OF_RANGE, "coc_scale >= 0");
+    h->denoise.lens = enable; // (read by the next pt_denoise_render; what is queued already took its values)
+    h->denoise.cocScale = coc_scale;
     return PT_OK;
 }
 

@@ -53,7 +53,11 @@ __global__ __launch_bounds__(256) void pt_guides_kernel(const FrameArgs a, float
     guides[2 * at + 1] = g1;
 }
 
-hipError_t launch_guides(const FrameArgs &args, float4 *guides, hipStream_t stream)
+// (pt_denoise_set_lens on: the same records from the pinhole ray; kernel and launch at the end of the file, behind the kernels that were
+// here before)
+static void launch_guides_pinhole(const FrameArgs &a, float4 *guides, int tiles, size_t lds, hipStream_t stream);
+
+hipError_t launch_guides(const FrameArgs &args, float4 *guides, bool pinhole, hipStream_t stream)
 {
     FrameArgs a = args;
     a.materialsInLds = 0; // (stage_scene: geometry only — the material table is the kernel's id table)
@@ -62,7 +66,8 @@ hipError_t launch_guides(const FrameArgs &args, float4 *guides, hipStream_t stre
     if (a.tilesX < 1 || a.tilesY < 1) return hipErrorInvalidValue;
     const int tiles = a.tilesX * a.tilesY;
     const size_t lds = scene_lds_bytes(a.numSpheres, a.numCuboids, 0, false) + (size_t)(a.numSpheres + a.numCuboids) * 4 * sizeof(float4);
-    hipLaunchKernelGGL(pt_guides_kernel, dim3((tiles + 3) / 4), dim3(256), lds, stream, a, guides);
+    if (pinhole) launch_guides_pinhole(a, guides, tiles, lds, stream);
+    else hipLaunchKernelGGL(pt_guides_kernel, dim3((tiles + 3) / 4), dim3(256), lds, stream, a, guides);
     return hipGetLastError();
 }
 
@@ -99,7 +104,17 @@ PT_DEV void dn_guide_weights(const float4 &g0p, const float4 &g1p, const float4 
 // estimate of stage V, since the accumulation image's alpha carries frame tags — and that of the output in colOut's alpha (a.last:
 // alpha = 1).  S = 1, 2: one more float per staged pixel, 52 bytes per pixel, 29,952 bytes at S = 2; S = 0: read with the colour.  The
 // fixed mode has no such array and reads neither a.varIn, a.k2 nor a.last; its alpha is not read and written as 1.
-template <int S, bool VARIANCE>
+// LENS (pt_denoise_set_lens on, a.cocK > 0): a pixel's blur radius is c = (cocK * |t - focal|) / t, c = cocK on a miss (dn_coc); a tap at
+// Chebyshev distance r = step * max(|dx|, |dy|) with r <= c(p) and r <= c(q) is relaxed: taken whatever its id, with wn = wz = 1.
+// S = 1, 2: c is evaluated once per staged pixel and staged where t was (no tap reads a neighbour's t; the centre fetches its own from
+// memory), so the LDS footprint is that of LENS = false.  S = 0: G1 is loaded where the id matches or r <= c(p), and c(q) divided out
+// only in the second case.
+PT_DEV float dn_coc(int id, float t, float cocK, float focal)
+{
+    return id == -1 ? cocK : (cocK * __builtin_fabsf(t - focal)) / t;
+}
+
+template <int S, bool VARIANCE, bool LENS>
 __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
 {
     constexpr int TX = S ? 16 : 64, TY = S ? 16 : 4, HALO = 2 * S, LW = TX + 2 * HALO, LH = TY + 2 * HALO;
@@ -117,8 +132,11 @@ __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
                 float4 c = a.colIn[at];
                 if constexpr (VARIANCE) sV[i] = a.varIn ? a.varIn[at] : c.w;
                 c.w = dn_u(c.x, c.y, c.z);
-                sG0[i] = a.guides[2 * at];
-                sG1[i] = a.guides[2 * at + 1];
+                const float4 g0 = a.guides[2 * at];
+                float4 g1 = a.guides[2 * at + 1];
+                if constexpr (LENS) g1.w = dn_coc(__float_as_int(g0.w), g1.w, a.cocK, a.focal);
+                sG0[i] = g0;
+                sG1[i] = g1;
                 sC[i] = c;
             }
         }
@@ -136,7 +154,10 @@ __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
     float4 out = make_float4(cp.x, cp.y, cp.z, varp);
     if (idp != -1) {
         const float up = S ? cp.w : dn_u(cp.x, cp.y, cp.z);
-        const float planeDen = a.sigmaPlane * g1p.w;
+        const float tp = S && LENS ? a.guides[2 * center + 1].w : g1p.w;
+        const float planeDen = a.sigmaPlane * tp;
+        float cocp = 0.0f;
+        if constexpr (LENS) cocp = S ? g1p.w : dn_coc(idp, tp, a.cocK, a.focal);
         float invp = 0.0f;
         if constexpr (VARIANCE) invp = 1.0f / (a.k2 * varp + 1e-8f);
         float W = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, Q = 0.0f;
@@ -152,13 +173,26 @@ __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
                 const size_t at = (size_t)qy * a.width + qx;
                 const int lq = lc + dy * S * LW + dx * S;
                 const float4 g0q = S ? sG0[lq] : a.guides[2 * at];
-                if (__float_as_int(g0q.w) != idp) continue;
-                const float4 g1q = S ? sG1[lq] : a.guides[2 * at + 1];
+                const int idq = __float_as_int(g0q.w);
+                float4 g1q;
+                bool relaxed = false;
+                if constexpr (LENS) {
+                    const float r = (float)(step * ((dx < 0 ? -dx : dx) > (dy < 0 ? -dy : dy) ? (dx < 0 ? -dx : dx) : (dy < 0 ? -dy : dy)));
+                    const bool reach = r <= cocp;
+                    if (idq != idp && !reach) continue;
+                    g1q = S ? sG1[lq] : a.guides[2 * at + 1];
+                    if (reach) relaxed = r <= (S ? g1q.w : dn_coc(idq, g1q.w, a.cocK, a.focal));
+                    if (idq != idp && !relaxed) continue;
+                } else {
+                    if (idq != idp) continue;
+                    g1q = S ? sG1[lq] : a.guides[2 * at + 1];
+                }
                 const float4 cq = S ? sC[lq] : a.colIn[at];
                 float varq = 0.0f;
                 if constexpr (VARIANCE) varq = S ? sV[lq] : (a.varIn ? a.varIn[at] : cq.w);
                 float wn, wz;
                 dn_guide_weights(g0p, g1p, g0q, g1q, planeDen, a.normalPower, wn, wz);
+                if (relaxed) wn = wz = 1.0f; // (w = h * wc)
                 const float uq = S ? cq.w : dn_u(cq.x, cq.y, cq.z);
                 float c1;
                 if constexpr (VARIANCE) {
@@ -186,26 +220,34 @@ __global__ __launch_bounds__(256) void pt_atrous_kernel(const AtrousArgs a)
 }
 
 // the mode's instantiation for the step
-template <bool VARIANCE>
+template <bool VARIANCE, bool LENS>
 void launch_atrous_steps(const AtrousArgs &a, hipStream_t stream)
 {
     if (a.step <= 2) {
         const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-        if (a.step == 1) hipLaunchKernelGGL((pt_atrous_kernel<1, VARIANCE>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((pt_atrous_kernel<2, VARIANCE>), grid, dim3(256), 0, stream, a);
+        if (a.step == 1) hipLaunchKernelGGL((pt_atrous_kernel<1, VARIANCE, LENS>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((pt_atrous_kernel<2, VARIANCE, LENS>), grid, dim3(256), 0, stream, a);
     } else {
-        hipLaunchKernelGGL((pt_atrous_kernel<0, VARIANCE>), dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((pt_atrous_kernel<0, VARIANCE, LENS>), dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
     }
 }
 // (the variance mode's three kernels are instantiated behind stage V: pt_variance_kernel<3> stays the sixth function of the file, and the
 // label numbering of its code — which the identity check compares — as it was)
-extern template void launch_atrous_steps<true>(const AtrousArgs &, hipStream_t);
+extern template void launch_atrous_steps<true, false>(const AtrousArgs &, hipStream_t);
+// (... and the six of LENS behind the temporal stage, at the end of the file)
+extern template void launch_atrous_steps<false, true>(const AtrousArgs &, hipStream_t);
+extern template void launch_atrous_steps<true, true>(const AtrousArgs &, hipStream_t);
 
 hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream)
 {
-    if (a.width < 1 || a.height < 1 || a.step < 1) return hipErrorInvalidValue;
-    if (a.variance) launch_atrous_steps<true>(a, stream);
-    else launch_atrous_steps<false>(a, stream);
+    if (a.width < 1 || a.height < 1 || a.step < 1 || (a.lens && !(a.cocK > 0.0f))) return hipErrorInvalidValue;
+    if (a.lens) {
+        if (a.variance) launch_atrous_steps<true, true>(a, stream);
+        else launch_atrous_steps<false, true>(a, stream);
+    } else {
+        if (a.variance) launch_atrous_steps<true, false>(a, stream);
+        else launch_atrous_steps<false, false>(a, stream);
+    }
     return hipGetLastError();
 }
 
@@ -236,7 +278,7 @@ hipError_t launch_denoise_copy(const float4 *in, float4 *out, size_t n, hipStrea
 // divided out once per staged cell.  Cells outside the image hold an id no guide record has, so "outside" and "another id" are one
 // comparison.  A lane keeps two window rows of 8 cells in registers (64 ds_read_b64 per pixel); Dx and Dy are formed from them and added
 // under selects in the order of the definition (dy outer, dx inner, Dx before Dy).
-// R = 3, the window's radius: a template so that the kernel is emitted behind pt_atrous_kernel<S, false> and leaves that code as it was.
+// R = 3, the window's radius: a template so that the kernel is emitted behind pt_atrous_kernel<S, false, false> and leaves that code as it was.
 constexpr int kVarOutsideId = (int)0x80000000;
 
 template <int R>
@@ -301,14 +343,14 @@ hipError_t launch_variance(const VarianceArgs &a, hipStream_t stream)
     return hipGetLastError();
 }
 
-template void launch_atrous_steps<true>(const AtrousArgs &, hipStream_t);
+template void launch_atrous_steps<true, false>(const AtrousArgs &, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------- temporal stage (pt_denoise_set_temporal)
 // I(p) = the image's (C, n) blended with the history set's I reprojected to p: the guide position of p goes through the
 // history camera's inverse ray matrix B to a point (fx, fy) of the history image, whose 2x2 neighbours of p's id are weighted by the
 // bilinear weight and the a-trous filter's own normal and plane weights (dn_guide_weights), and the weighted mean (colour Hc,
 // count m clamped to max_history) is mixed with C by sample counts: I = ((n C + m' Hc) / (n + m'), n + m').  One pixel per lane, 64x4
-// tiles as pt_atrous_kernel<0, *>: a wavefront is 64 adjacent pixels of one row, so the centre's three 16-byte loads coalesce; the four taps
+// tiles as pt_atrous_kernel<0, *, *>: a wavefront is 64 adjacent pixels of one row, so the centre's three 16-byte loads coalesce; the four taps
 // are data-dependent gathers — G0 first, G1 and I_h only where the id matches.  Every comparison is false for NaN, so a pixel whose
 // projection is not finite passes through.  fx lies in [-1, W) where taps are formed, so x0 = floor(fx) fits an int and every tap is
 // bounds-checked before its load.
@@ -381,5 +423,55 @@ hipError_t launch_temporal(const TemporalArgs &a, hipStream_t stream)
     hipLaunchKernelGGL(pt_temporal_kernel<2>, dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------- lens mode (pt_denoise_set_lens)
+// The guide records of the pixel-centre pinhole ray (pinhole_ray) instead of sample 0: the same fields by the same rules — id and t as
+// pt_first_hit_pinhole_kernel writes them, P = origin + direction * t in two roundings per component — and a.frame is not read.
+// PINHOLE = true: a template so that the kernel is emitted behind the others and leaves their code (its label numbering) as it was;
+// sample 0 is pt_guides_kernel.
+template <bool PINHOLE>
+__global__ __launch_bounds__(256) void pt_guides_ray_kernel(const FrameArgs a, float4 *guides)
+{
+    static_assert(PINHOLE, "the guides of sample 0 are pt_guides_kernel's");
+    SceneLds sc = stage_scene(a);
+    const int tid = threadIdx.x;
+    const int ns = a.numSpheres, nc = a.numCuboids;
+    float4 *ids = g_lds + scene_lds_bytes(ns, nc, 0, false) / sizeof(float4);
+    for (int i = tid; i < ns + nc; i += 256) ids[4 * i] = make_float4((float)(i < ns ? i : kFirstHitCuboidBase + (i - ns)), 0.0f, 0.0f, 0.0f);
+    __syncthreads();
+    sc.mat = ids;
+    const int b = xcd_band_id(blockIdx.x, gridDim.x);
+    const int wave = tid >> 6, lane = tid & 63;
+    const int tile = b * 4 + wave;
+    if (tile >= a.tilesX * a.tilesY) return;
+    const int tx = tile % a.tilesX, ty = tile / a.tilesX;
+    const int px = tx * 8 + (lane & 7);
+    const int ly = ty * 8 + (lane >> 3);
+    if (px >= a.width || ly >= a.rows) return;
+#ifdef PT_PROFILE
+    unsigned long long prof_dummy[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    v3 ro, rd;
+    pinhole_ray(a, px, global_row(a, ly), ro, rd);
+    Hit h;
+    const bool hit = ray_trace(sc, ns, nc, ro, rd, h PROF_DUMMY); // :226-258
+    float4 g0 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+    float4 g1 = make_float4(0.0f, 0.0f, 0.0f, __builtin_inff());
+    if (hit) {
+        g0 = make_float4(rd.x * h.T + ro.x, rd.y * h.T + ro.y, rd.z * h.T + ro.z, __int_as_float((int)h.m.albedo.x));
+        g1 = make_float4(h.normal.x, h.normal.y, h.normal.z, h.T);
+    }
+    const size_t at = (size_t)ly * a.width + px;
+    guides[2 * at] = g0;
+    guides[2 * at + 1] = g1;
+}
+
+static void launch_guides_pinhole(const FrameArgs &a, float4 *guides, int tiles, size_t lds, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pt_guides_ray_kernel<true>, dim3((tiles + 3) / 4), dim3(256), lds, stream, a, guides);
+}
+
+template void launch_atrous_steps<false, true>(const AtrousArgs &, hipStream_t);
+template void launch_atrous_steps<true, true>(const AtrousArgs &, hipStream_t);
 
 } // namespace pt

@@ -905,6 +905,20 @@ PT_DEV void primary_ray(const FrameArgs &a, int px, int py, uint32_t &seed, v3 &
     primary_ray_cam<const float *>(a.invProj, a.invW, a.invH, px, py, seed, ro, rd);
 }
 
+// The pixel-centre pinhole ray (PT_RAY_PINHOLE, pt_denoise_set_lens): primary_ray_cam's NDC, GetWorldSpaceRay (:352-357) and normalisation
+// with u0 = u1 = 0.5f and no lens — the origin is InvView's translation column (the bits InvView * (0, 0, 0, 1) of :120 gives at aperture
+// 0), the direction is `dir` itself, not taken through the focal point.  No RNG draw; frame, focal length and aperture do not enter.
+PT_DEV void pinhole_ray(const FrameArgs &a, int px, int py, v3 &ro, v3 &rd)
+{
+    float ndcx = f_fma(((float)px + 0.5f) * a.invW, 2.0f, -1.0f);
+    float ndcy = f_fma(((float)py + 0.5f) * a.invH, 2.0f, -1.0f);
+    float eye[4], wd[4];
+    mat_vec(a.invProj, ndcx, ndcy, -1.0f, 0.0f, eye);
+    mat_vec(a.invView, eye[0], eye[1], -1.0f, 0.0f, wd);
+    ro = V(a.invView[12], a.invView[13], a.invView[14]);
+    rd = v_normalize(V(wd[0], wd[1], wd[2]));
+}
+
 // image row of local row `ly` of this launch (contiguous row block, or block-cyclic bands across GPUs)
 PT_DEV int global_row_v(int bandRows, int bandWorld, int bandRank, int localRow0, int y0, int ly)
 {

@@ -222,16 +222,18 @@ hipError_t launch_repair_done(unsigned int *abandonWord, unsigned int *queueMain
                               unsigned int expectChain, unsigned int *ctl, hipStream_t stream);
 // the first-hit query (pt_first_hit.hip; contract arithmetic): per pixel of the launch (a.tilesX / a.tilesY set, a.frame = the frame whose
 // sample 0 is traced) two float4 — (origin, t) and (direction, id bits: -1 miss, sphere i, kFirstHitCuboidBase + cuboid j).  pickTile < 0:
-// records = rows x width x 2 float4; pickTile >= 0: only that tile, one workgroup, lane l of the tile at records[2 * l] (64 x 2 float4)
+// records = rows x width x 2 float4; pickTile >= 0: only that tile, one workgroup, lane l of the tile at records[2 * l] (64 x 2 float4).
+// pinhole (PT_RAY_PINHOLE): the pixel-centre pinhole ray (pinhole_ray) instead of sample 0; a.frame is then not read
 constexpr int kFirstHitCuboidBase = 256; // PT_MAX_SPHERES (the winner numbering of ray_trace_t)
-hipError_t launch_first_hit(const FrameArgs &a, float4 *records, int pickTile, hipStream_t stream);
+hipError_t launch_first_hit(const FrameArgs &a, float4 *records, int pickTile, bool pinhole, hipStream_t stream);
 // the preview denoiser (pt_denoise.hip).  Guides: per pixel of the launch (fields as for launch_first_hit) two float4 —
-// (P.xyz, id bits) and (N.xyz, t), id / t as the first-hit record's.
-hipError_t launch_guides(const FrameArgs &a, float4 *guides, hipStream_t stream);
+// (P.xyz, id bits) and (N.xyz, t), id / t as the first-hit record's; pinhole (pt_denoise_set_lens on): of the pinhole ray's record.
+hipError_t launch_guides(const FrameArgs &a, float4 *guides, bool pinhole, hipStream_t stream);
 // one a-trous pass colIn -> colOut over a width x height image (compact rows).  Fixed mode (variance = 0): colIn's alpha is not read,
 // colOut's is 1; varIn, k2 and last are not read.  Variance-guided mode (PT_DENOISE_VARIANCE; variance = 1): the variance of the input is
 // varIn (pass 0: stage V's buffer) or, where varIn is null, colIn's alpha; that of the output is colOut's alpha, or alpha = 1 on the last
-// pass; invSigma is not read
+// pass; invSigma is not read.  lens = 1 (pt_denoise_set_lens on, cocK > 0): a tap within the lens's blur radius of both its ends is taken
+// on the luminance stop alone; lens = 0: cocK and focal are not read
 struct AtrousArgs {
     const float4 *colIn;
     const float *varIn;
@@ -245,6 +247,9 @@ struct AtrousArgs {
     float sigmaPlane;
     int normalPower;  // the normal weight is squared this many times
     int last;         // the last pass writes alpha 1
+    int lens;         // 1: relaxed taps; needs cocK > 0
+    float cocK;       // the blur radius in pixels per unit of |t - focal| / t, computed by the host in double and rounded once
+    float focal;      // the focal length
 };
 hipError_t launch_atrous(const AtrousArgs &a, hipStream_t stream);
 hipError_t launch_denoise_copy(const float4 *in, float4 *out, size_t pixels, hipStream_t stream); // out = (in.rgb, 1)

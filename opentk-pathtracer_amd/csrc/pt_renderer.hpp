@@ -169,6 +169,7 @@ struct pt_renderer {
     // since.  dPick: the 64 records of the one tile a pt_pick traces.
     float4 *dFirstHit = nullptr;
     float4 *dPick = nullptr;
+    int firstHitRay = 0; // PT_RAY_SAMPLE0 (pt_first_hit_set_ray): the ray of the pt_first_hit_render / pt_pick calls that follow
     // Temporal stage of the denoiser (pt_denoise_set_temporal).  A set = one integrated image (rgb, count), one guide buffer (beside dGuides,
     // which the renders with the stage off keep to themselves), the camera it was made under (B = the inverse of the ray matrix, O = the
     // ray origin), the reset epoch it was made in and a valid flag.
@@ -200,6 +201,9 @@ struct pt_renderer {
         int temporal = 0, maxHistory = 32;
         bool integratedValid = false; // the last pt_denoise_render ran with the stage on (its I and guides are the current set's) ...
         bool historyUsed = false;     // ... and read a valid history set
+        // Lens mode (pt_denoise_set_lens): guides from the pinhole ray, and taps within the lens's blur radius relaxed (coc_scale > 0)
+        int lens = 0;
+        float cocScale = 1.0f;
 
         bool allocated() const
         {

@@ -314,6 +314,9 @@ public:
         Check(pt_first_hit_read(h_, rec.data(), 0), h_);
         return rec;
     }
+    // the ray of the FirstHit() / Pick() calls that follow: PT_RAY_SAMPLE0 (the default) or PT_RAY_PINHOLE — the pinhole ray through the
+    // pixel's centre, the same for every frame, focal length and aperture (a stable click with the lens open)
+    void SetFirstHitRay(int mode) { Check(pt_first_hit_set_ray(h_, mode), h_); }
     // one pixel (y = 0 is the bottom row)
     FirstHitRecord Pick(int x, int y, int frame = 0) const
     {
@@ -386,6 +389,9 @@ public:
         Check(pt_denoise_read_history(h_, s.image.data(), s.guides.data(), s.B, s.O), h_);
         return s;
     }
+    // lens mode for the Denoise() calls that follow, for a host that renders with the lens open (MainWindow.cs:189): guides from the pinhole
+    // ray through the pixel's centre, and taps within cocScale times the lens's blur radius of both their ends taken on the luminance stop alone
+    void SetDenoiseLens(bool enable = true, float cocScale = 1.0f) { Check(pt_denoise_set_lens(h_, enable ? 1 : 0, cocScale), h_); }
     // ScreenEffect.Render (src/Render/ScreenEffect.cs:29-37) of the last Denoise() instead of `Result`
     std::vector<uint8_t> PresentDenoised() const
     {

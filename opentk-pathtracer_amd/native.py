@@ -32,6 +32,7 @@ PT_ENV_RGBA32F, PT_ENV_SRGB8_A8 = 0, 1
 PT_MAX_SPHERES, PT_MAX_CUBOIDS = 256, 64  # first-hit ids: sphere i = i, cuboid j = PT_MAX_SPHERES + j, miss = -1
 PT_ARITH_CONTRACT, PT_ARITH_REFERENCE = 0, 1  # pt_set_arithmetic, pt_atmosphere_set_arithmetic, pt_present_set_arithmetic
 PT_DENOISE_FIXED, PT_DENOISE_VARIANCE = 0, 1  # pt_denoise_set_mode
+PT_RAY_SAMPLE0, PT_RAY_PINHOLE = 0, 1  # pt_first_hit_set_ray
 
 
 class NativeError(RuntimeError):
@@ -212,6 +213,7 @@ def load() -> C.CDLL:
         "pt_present_wait": [vp, C.c_int, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), ip],
         "pt_present_bind_device_image": [vp, C.c_int, vp, C.c_size_t],
         "pt_present_set_arithmetic": [vp, C.c_int],
+        "pt_first_hit_set_ray": [vp, C.c_int],
         "pt_first_hit_render": [vp, C.c_int],
         "pt_first_hit_read": [vp, vp, C.c_size_t],
         "pt_first_hit_device_ptr": [vp, C.POINTER(vp), C.POINTER(C.c_size_t)],
@@ -228,6 +230,7 @@ def load() -> C.CDLL:
         "pt_denoise_history_clear": [vp],
         "pt_denoise_read_integrated": [vp, fp, C.c_size_t],
         "pt_denoise_read_history": [vp, fp, vp, fp, fp],
+        "pt_denoise_set_lens": [vp, C.c_int, C.c_float],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -287,6 +287,12 @@ class PathTracer:
         check(self._lib.pt_first_hit_read(self._h, out.ctypes.data_as(C.c_void_p), 0), self._h)
         return out
 
+    def SetFirstHitRay(self, mode: int) -> None:
+        """pt_first_hit_set_ray: the ray of the FirstHit and Pick calls that follow — native.PT_RAY_SAMPLE0 (sample 0 of `frame`, lens and
+        sub-pixel draws included; the default) or native.PT_RAY_PINHOLE (the pinhole ray through the pixel's centre: the same answer for
+        every frame, focal length and aperture)."""
+        check(self._lib.pt_first_hit_set_ray(self._h, mode), self._h)
+
     def Pick(self, x: int, y: int, frame: int = 0):
         """pt_pick: -> (id, t, origin (3,), dir (3,)) of image pixel (x, y) (y = 0 is the bottom row) for sample 0 of `frame`."""
         i, t = C.c_int(), C.c_float()
@@ -352,6 +358,12 @@ class PathTracer:
         check(self._lib.pt_denoise_read_history(self._h, image.ctypes.data_as(fp), guides.ctypes.data_as(C.c_void_p), B.ctypes.data_as(fp),
                                                 O.ctypes.data_as(fp)), self._h)
         return image, guides, B, O
+
+    def SetDenoiseLens(self, enable: bool = True, coc_scale: float = 1.0) -> None:
+        """pt_denoise_set_lens: the Denoise calls that follow take their guides from the pinhole ray through the pixel's centre instead
+        of sample 0, and relax the id, normal and plane stops of a tap that lies within coc_scale times the lens's blur radius of both
+        its ends (coc_scale 0: pinhole guides, the usual tap rules).  For a host that renders with the lens open."""
+        check(self._lib.pt_denoise_set_lens(self._h, int(enable), coc_scale), self._h)
 
     def PresentDenoised(self) -> np.ndarray:
         """pt_denoise_present_rgba8: the result of the last Denoise through the tone map Present applies, as (rows, Width, 4) uint8."""
