@@ -426,7 +426,10 @@ PT_API int pt_denoise_read_variance(pt_handle h, float *dst, size_t row_pitch_by
 PT_API int pt_denoise_set_temporal(pt_handle h, int enable, int max_history);
 /* Forgets both sets: the next temporal pt_denoise_render finds no history (I = (C, n)) — what a host calls after a scene, material or
  * environment edit (the GUI edits beside the camera moves of MainWindow.cs:49-63, shown through ScreenEffect.cs:29-37), which changes
- * the colours the history holds, not only where they are seen from.  Frees nothing.  Scope as for pt_denoise_set_params. */
+ * the colours the history holds, not only where they are seen from.  With pt_denoise_set_object_tracking on, an edit of the objects
+ * (position, size, material, the counts) needs no clear: the stage follows or drops the edited object's history by itself.  An
+ * environment edit, a pt_set_params change other than the counts (ray depth, spp, lens) and anything else the scene blob does not hold
+ * still do.  Frees nothing.  Scope as for pt_denoise_set_params. */
 PT_API int pt_denoise_history_clear(pt_handle h);
 /* The integrated image I of the last pt_denoise_render made with the temporal stage on — the input of the passes in place of the image
  * of MainWindow.cs:49-63, before the filter and ScreenEffect.cs:29-37 — RGBA32F, alpha = the per-pixel sample count (it doubles as a
@@ -439,6 +442,33 @@ PT_API int pt_denoise_read_integrated(pt_handle h, float *dst, size_t row_pitch_
  * out_B (P - out_O) = lambda (ndc x, ndc y, 1) for a point P seen by that camera.  Every pointer may be NULL.  PT_E_BAD_ARGUMENT when
  * that render had no history (or none was made since the last (re)size / (re)tiling / pt_denoise_history_clear). */
 PT_API int pt_denoise_read_history(pt_handle h, float *image, void *guides, float out_B[9], float out_O[3]);
+
+/* Object tracking of the temporal stage, for the other everyday reset: the object-properties window,
+ * Gui.cs:154-218 (Position drag :163-168, material fields :170-210, Upload + reset :212-216), MainWindow.cs:58-63.  Every temporal
+ * pt_denoise_render keeps, with its set, a copy of the scene blob and the object counts.  With tracking on, a render with a valid history
+ * compares that copy with the scene in force, object by object (guide ids are object indices), into an OBJECT MAP of 320 entries of 32
+ * bytes, indexed by guide id (sphere i at i, cuboid j at PT_MAX_SPHERES + j): words 0-2 a.xyz, word 3 the state as int32 bits, words 4-6
+ * b.xyz, word 7 zero.  PT_TRACK_DROP: the id is beyond either scene's count of its kind, or one of its 64 material bytes differs — its
+ * pixels take no history (I = (C, n)).  PT_TRACK_KEEP (a = 1, b = 0): its geometry floats are bit-equal.  PT_TRACK_MOVED: they differ —
+ * a translation or a resize, the edits of Gui.cs:163-168 / Cuboid.cs:23-24 — and history point = a * P + b per component carries the
+ * object as it is onto the object as the history saw it (sphere: a = r_h / r_c; cuboid, per axis: a = extent_h / extent_c; in double,
+ * rounded once; a radius or extent <= 0 or anything not finite: DROP): the history of a pixel is sought at that point instead of at P,
+ * among the pixels of its id.  If every object that exists is KEEP and the counts are equal, the render is bit for bit what it is with
+ * tracking off; otherwise the count a history pixel brings along is capped by min(max_history, edit_max_history) (edit_max_history 0:
+ * by max_history), since the edit also changed the light that falls on everything else.  Through ScreenEffect.cs:29-37 as before. */
+enum { PT_TRACK_KEEP = 0, PT_TRACK_MOVED = 1, PT_TRACK_DROP = 2 };
+/* Switch of the pt_denoise_render calls that follow — what a host sets once, so that the Upload + reset of Gui.cs:154-218 (Position drag
+ * :163-168, material fields :170-210, Upload + reset :212-216; the reset of MainWindow.cs:58-63) needs no pt_denoise_history_clear; the
+ * result is shown through ScreenEffect.cs:29-37; what is queued already keeps the values it was issued under.  enable: 0 or 1, anything
+ * else PT_E_BAD_ARGUMENT; edit_max_history 0..65535, outside that PT_E_OUT_OF_RANGE; the previous values stay in force then.  Defaults
+ * 0, 0.  No effect unless pt_denoise_set_temporal is on.  Scope as for pt_denoise_set_params. */
+PT_API int pt_denoise_set_object_tracking(pt_handle h, int enable, int edit_max_history);
+/* The object map the last pt_denoise_render built for the edit of Gui.cs:154-218 (Position drag :163-168, material fields :170-210,
+ * Upload + reset :212-216) that the reset of MainWindow.cs:58-63 followed, before its result went to ScreenEffect.cs:29-37: 320 entries of
+ * 32 bytes as above into dst_320x32_bytes; *out_tracked = 1 if the scene differed and the tracked kernel ran, 0 if it was unchanged (all
+ * KEEP).  Either pointer may be NULL.  PT_E_BAD_ARGUMENT when the last render ran with the temporal stage or this switch off, when it had
+ * no valid history, or when nothing was rendered since the last (re)size / (re)tiling / pt_denoise_history_clear. */
+PT_API int pt_denoise_read_object_map(pt_handle h, void *dst_320x32_bytes, int *out_tracked);
 
 /* Lens mode of the pt_denoise_render calls that follow, for a host that renders with the lens open (the reference's own start:
  * new PathTracer(env, W, H, 13, 1, 20f, 0.14f), MainWindow.cs:189, shown through MainWindow.cs:49-63 / ScreenEffect.cs:29-37); what is

@@ -2,6 +2,7 @@
 // first-hit query (pt_first_hit_*, pt_pick) and the preview denoiser (pt_denoise_*).  Both stand behind bind_device / join_stripes and
 // use nothing else of the launch pipeline of mi355pt.cpp; their buffers belong to a size and a tiling (free_first_hit, free_denoise).
 #include "pt_renderer.hpp"
+#include "pt_object_map.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -28,6 +29,7 @@ int free_denoise(pt_handle h)
     d.result = -1;
     d.varianceValid = false;
     d.integratedValid = d.historyUsed = false;
+    d.mapValid = d.mapTracked = false;
     for (pt_renderer::DenoiseSet &set : d.set) set.valid = false;
     if (!d.allocated()) return PT_OK;
     PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_denoise_render may still write them)
@@ -208,6 +210,16 @@ static float denoise_coc_k(pt_handle h)
     return std::isfinite(k) ? k : 0.0f;
 }
 
+// The object map of a temporal render with tracking on (pt_object_map.hpp): the history set's scene snapshot against the
+// scene in force.  -> the tracked kernel has to run
+static_assert(pt::kObjectMapEntries == ptmap::kEntries && ptmap::kMaxSpheres == PT_MAX_SPHERES && ptmap::kMaxCuboids == PT_MAX_CUBOIDS, "object map: one entry per guide id");
+static_assert(pt::kTrackKeep == PT_TRACK_KEEP && pt::kTrackMoved == PT_TRACK_MOVED && pt::kTrackDrop == PT_TRACK_DROP, "object map states");
+static_assert(ptmap::kKeep == PT_TRACK_KEEP && ptmap::kMoved == PT_TRACK_MOVED && ptmap::kDrop == PT_TRACK_DROP, "object map states");
+static bool denoise_object_map(const pt_renderer::DenoiseSet &hist, const unsigned char *scene, int ns, int nc, unsigned char *map)
+{
+    return ptmap::build(hist.scene, hist.numSpheres, hist.numCuboids, scene, ns, nc, map);
+}
+
 // stage kDenoiseAll: everything; -1: the guides only; kDenoiseStageV: stage V of the variance mode only; kDenoiseStageT: the temporal
 // kernel only; i >= 0: pass i only (pt_debug_denoise_stage, for timing)
 constexpr int kDenoiseStageV = -2, kDenoiseAll = -3, kDenoiseStageT = -4;
@@ -262,13 +274,35 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
         std::memcpy(t.O, hist.O, sizeof t.O);
         t.sigmaPlane = d.sigmaPlane;
         t.normalPower = d.normalPower;
-        PT_HIP(h, pt::launch_temporal(t, h->stream));
+        // object tracking: a full render builds the map and, where the scene differs from the history's, uploads it (stream-ordered, as
+        // pt_upload_game_objects uploads the blob: a pageable source is staged before the call returns); a timing stage runs the kernel
+        // the last full render selected, with the map that render left on the device
+        if (stage == kDenoiseAll) {
+            d.mapValid = d.tracking != 0 && hist.valid;
+            d.mapTracked = d.mapValid && denoise_object_map(hist, h->objectsShadow, h->numSpheres, h->numCuboids, d.objectMap);
+            if (d.mapTracked) {
+                if (!d.dObjectMap) PT_HIP(h, hipMalloc((void **)&d.dObjectMap, sizeof d.objectMap));
+                PT_HIP(h, hipMemcpyAsync(d.dObjectMap, d.objectMap, sizeof d.objectMap, hipMemcpyHostToDevice, h->stream));
+            }
+        }
+        if (d.tracking != 0 && d.mapTracked && hist.valid && d.dObjectMap) {
+            if (d.editMaxHistory != 0 && d.editMaxHistory < d.maxHistory) t.maxHistory = (float)d.editMaxHistory; // the cap of a tracked render
+            PT_HIP(h, pt::launch_temporal_tracked(t, d.dObjectMap, h->stream));
+        } else {
+            PT_HIP(h, pt::launch_temporal(t, h->stream));
+        }
         if (stage == kDenoiseStageT) return PT_OK;
         cur.valid = denoise_set_camera(h->basic, cur.B, cur.O);
         cur.epoch = h->resetEpoch;
+        std::memcpy(cur.scene, h->objectsShadow, sizeof cur.scene); // (whatever the tracking switch says: a later render may compare against it)
+        cur.numSpheres = h->numSpheres;
+        cur.numCuboids = h->numCuboids;
         d.historyUsed = hist.valid;
     }
-    if (stage == kDenoiseAll) d.integratedValid = temporal;
+    if (stage == kDenoiseAll) {
+        d.integratedValid = temporal;
+        if (!temporal) d.mapValid = d.mapTracked = false;
+    }
     const int n = d.iterations;
     if (n == 0 && stage == kDenoiseAll) PT_HIP(h, pt::launch_denoise_copy(first, d.dImage[0], pixels, h->stream));
     if (variance && n > 0 && (stage == kDenoiseAll || stage == kDenoiseStageV)) {
@@ -413,6 +447,29 @@ PT_API int pt_denoise_history_clear(pt_handle h)
     if (int rc = denoise_owner(h)) return rc;
     for (pt_renderer::DenoiseSet &set : h->denoise.set) set.valid = false; // (the buffers stay: a queued render may still read them)
     h->denoise.historyUsed = false;
+    h->denoise.mapValid = h->denoise.mapTracked = false;
+    return PT_OK;
+}
+
+PT_API int pt_denoise_set_object_tracking(pt_handle h, int enable, int edit_max_history)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    if (enable != 0 && enable != 1) return fail(h, PT_E_BAD_ARGUMENT, "enable must be 0 or 1");
+    if (edit_max_history < 0 || edit_max_history > 65535) return fail(h, PT_E_OUT_OF_RANGE, "edit_max_history 0..65535");
+    h->denoise.tracking = enable; // (read by the next pt_denoise_render; what is queued already took its values)
+    h->denoise.editMaxHistory = edit_max_history;
+    return PT_OK;
+}
+
+PT_API int pt_denoise_read_object_map(pt_handle h, void *dst_320x32_bytes, int *out_tracked)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    if (!h->denoise.mapValid)
+        return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render built no object map (temporal stage or tracking off, no history, or nothing rendered since)");
+    if (dst_320x32_bytes) std::memcpy(dst_320x32_bytes, h->denoise.objectMap, sizeof h->denoise.objectMap);
+    if (out_tracked) *out_tracked = h->denoise.mapTracked ? 1 : 0;
     return PT_OK;
 }
 
@@ -462,7 +519,8 @@ PT_API int pt_denoise_present_rgba8(pt_handle h, uint8_t *dst, size_t row_pitch_
 
 // Timing aid (not declared in the public header): one stage of pt_denoise_render on its own — stage -1 = the guide kernel, i >= 0 = pass i
 // of the mode in force, -2 = stage V (the variance estimate; PT_DENOISE_VARIANCE only), -4 = the temporal kernel (pt_denoise_set_temporal
-// on only) — between the buffers a full render uses (a pt_denoise_render must have run, with the temporal switch as it stands now; the
+// on only; whichever of pt_temporal_kernel / pt_temporal_tracked_kernel the last pt_denoise_render selected, with the object map it
+// left) — between the buffers a full render uses (a pt_denoise_render must have run, with the temporal switch as it stands now; the
 // result it left is overwritten with a partial one; the sets are neither swapped nor marked).
 extern "C" __attribute__((visibility("default"))) int pt_debug_denoise_stage(pt_handle h, int guide_frame_index, int stage)
 {

@@ -474,4 +474,94 @@ static void launch_guides_pinhole(const FrameArgs &a, float4 *guides, int tiles,
 template void launch_atrous_steps<false, true>(const AtrousArgs &, hipStream_t);
 template void launch_atrous_steps<true, true>(const AtrousArgs &, hipStream_t);
 
+// ---------------------------------------------------------------------------------------------- object tracking (pt_denoise_set_object_tracking)
+// pt_temporal_kernel<2> for a render whose scene differs from the history's: the object map entry of p's id says where the
+// history of p is — KEEP: at P_p, MOVED: at P' = a * P_p + b (two roundings per component: the object's own translation / resize),
+// DROP: nowhere, the pixel passes through — and P' stands in for P_p in the projection and in the plane term of every tap; everything
+// else (normal weight, planeDen = sigma_plane * t_p, bilinear weights, tap order, id test, blend) is that kernel's, a.maxHistory the cap
+// of a tracked render.  Same shape: 64x4 tiles, one pixel per lane.  The map (10,240 B) is gathered from memory, not staged in LDS: a
+// lane needs one 16-byte entry half (the state and a) and the second (b) only where its object moved, a wavefront — 64 adjacent pixels
+// of one row — sees a handful of ids, so the gather touches a few cache lines of a table that stays resident in the CU's 32 KiB L1;
+// staging would load 640 float4 per 256 pixels (2.5 loads, 2.5 LDS writes and a barrier per lane) to save at most two loads per lane.
+// TAPS = 2 as there: a template so that the kernel is emitted behind the others and leaves their code as it was.
+template <int TAPS>
+__global__ __launch_bounds__(256) void pt_temporal_tracked_kernel(const TemporalArgs a, const float4 *objectMap)
+{
+    static_assert(TAPS == 2, "the definition's 2x2 bilinear footprint");
+    const int tid = threadIdx.x;
+    const int px = blockIdx.x * 64 + (tid & 63), py = blockIdx.y * 4 + (tid >> 6);
+    if (px >= a.width || py >= a.height) return;
+    const size_t center = (size_t)py * a.width + px;
+    const float4 cp = a.colIn[center];
+    float4 out = make_float4(cp.x, cp.y, cp.z, a.n);
+    const float4 g0p = a.guides[2 * center];
+    const int idp = __float_as_int(g0p.w);
+    if ((unsigned)idp < (unsigned)kObjectMapEntries) { // (a miss, id -1, reads no entry; no guide record holds another id)
+        const float4 ma = objectMap[2 * idp];
+        const int state = __float_as_int(ma.w);
+        if (state == kTrackKeep || state == kTrackMoved) {
+            float4 g0t = g0p; // (P', id)
+            if (state == kTrackMoved) {
+                const float4 mb = objectMap[2 * idp + 1];
+                g0t.x = ma.x * g0p.x + mb.x;
+                g0t.y = ma.y * g0p.y + mb.y;
+                g0t.z = ma.z * g0p.z + mb.z;
+            }
+            const float4 g1p = a.guides[2 * center + 1];
+            const float dx = g0t.x - a.O[0], dy = g0t.y - a.O[1], dz = g0t.z - a.O[2];
+            const float x = (a.B[0] * dx + a.B[1] * dy) + a.B[2] * dz;
+            const float y = (a.B[3] * dx + a.B[4] * dy) + a.B[5] * dz;
+            const float z = (a.B[6] * dx + a.B[7] * dy) + a.B[8] * dz;
+            const float fw = (float)a.width, fh = (float)a.height;
+            const float fx = ((x / z) * 0.5f + 0.5f) * fw - 0.5f;
+            const float fy = ((y / z) * 0.5f + 0.5f) * fh - 0.5f;
+            if (z > 0.0f && fx >= -1.0f && fx < fw && fy >= -1.0f && fy < fh) {
+                const float flx = __builtin_floorf(fx), fly = __builtin_floorf(fy);
+                const float ax = fx - flx, ay = fy - fly;
+                const int x0 = (int)flx, y0 = (int)fly;
+                const float planeDen = a.sigmaPlane * g1p.w;
+                float Wh = 0.0f, Sr = 0.0f, Sg = 0.0f, Sb = 0.0f, Mh = 0.0f;
+#pragma unroll
+                for (int j = 0; j < TAPS; j++) {
+#pragma unroll
+                    for (int i = 0; i < TAPS; i++) {
+                        const int qx = x0 + i, qy = y0 + j;
+                        if (qx < 0 || qx >= a.width || qy < 0 || qy >= a.height) continue;
+                        const size_t at = (size_t)qy * a.width + qx;
+                        const float4 g0q = a.histGuides[2 * at];
+                        if (__float_as_int(g0q.w) != idp) continue;
+                        const float4 g1q = a.histGuides[2 * at + 1];
+                        const float4 hq = a.histImage[at];
+                        const float bw = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+                        float wn, wz;
+                        dn_guide_weights(g0t, g1p, g0q, g1q, planeDen, a.normalPower, wn, wz); // (the plane term: N_p . (P_h(q) - P'))
+                        const float w = (bw * wn) * wz;
+                        Wh = Wh + w;
+                        Sr = Sr + w * hq.x;
+                        Sg = Sg + w * hq.y;
+                        Sb = Sb + w * hq.z;
+                        Mh = Mh + w * hq.w;
+                    }
+                }
+                if (Wh > 0.0f) {
+                    const float m = Mh / Wh;
+                    const float mc = m < a.maxHistory ? m : a.maxHistory;
+                    const float den = a.n + mc;
+                    if (den > 0.0f)
+                        out = make_float4((a.n * cp.x + mc * (Sr / Wh)) / den, (a.n * cp.y + mc * (Sg / Wh)) / den,
+                                          (a.n * cp.z + mc * (Sb / Wh)) / den, den);
+                }
+            }
+        }
+    }
+    a.out[center] = out;
+}
+
+hipError_t launch_temporal_tracked(const TemporalArgs &a, const float4 *objectMap, hipStream_t stream)
+{
+    if (a.width < 1 || a.height < 1 || !a.histImage || !a.histGuides || !objectMap) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_temporal_tracked_kernel<2>, dim3((a.width + 63) / 64, (a.height + 3) / 4), dim3(256), 0, stream, a, objectMap);
+    return hipGetLastError();
+}
+
 } // namespace pt

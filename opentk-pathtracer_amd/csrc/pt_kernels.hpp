@@ -278,6 +278,14 @@ struct TemporalArgs {
     int normalPower;
 };
 hipError_t launch_temporal(const TemporalArgs &a, hipStream_t stream);
+// the same stage with object tracking (pt_denoise_set_object_tracking) for a render whose scene differs from the history's: per guide id
+// (sphere i at i, cuboid j at kFirstHitCuboidBase + j) objectMap holds (a.xyz, state bits) and (b.xyz, 0) — state kTrackKeep: the history
+// is sought at P, kTrackMoved: at a * P + b per component (the object's own motion), kTrackDrop: not at all (the pixel passes through);
+// maxHistory carries the cap of a tracked render.  Needs a valid history (histImage != null) and the map, which travels as a kernel
+// argument of its own: TemporalArgs, and with it the code object of pt_temporal_kernel, stays byte for byte what it was
+constexpr int kObjectMapEntries = 320; // PT_MAX_SPHERES + PT_MAX_CUBOIDS
+constexpr int kTrackKeep = 0, kTrackMoved = 1, kTrackDrop = 2;
+hipError_t launch_temporal_tracked(const TemporalArgs &a, const float4 *objectMap, hipStream_t stream);
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 // the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);

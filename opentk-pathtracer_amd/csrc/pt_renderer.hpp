@@ -178,6 +178,9 @@ struct pt_renderer {
         float B[9] = {0}, O[3] = {0};
         unsigned long long epoch = 0;
         bool valid = false;
+        // object tracking (pt_denoise_set_object_tracking): the scene the set was made of — a copy of objectsShadow and the counts in force
+        unsigned char scene[PT_GAME_OBJECTS_UBO_SIZE] = {0};
+        int numSpheres = 0, numCuboids = 0;
     };
     struct Denoiser {
         // Preview denoiser (pt_denoise_render, pt_denoise.hip): rows x width guide records of 32 bytes and the two ping-pong images of the
@@ -204,10 +207,18 @@ struct pt_renderer {
         // Lens mode (pt_denoise_set_lens): guides from the pinhole ray, and taps within the lens's blur radius relaxed (coc_scale > 0)
         int lens = 0;
         float cocScale = 1.0f;
+        // Object tracking of the temporal stage (pt_denoise_set_object_tracking): objectMap = the map the last pt_denoise_render built
+        // (kObjectMapEntries entries of 32 bytes, by guide id) — mapValid: it built one (stage and switch on, a valid history),
+        // mapTracked: the scene differed and the tracked kernel ran with it; dObjectMap = its device copy, allocated by the first
+        // tracked render after a (re)size or (re)tiling and freed with the buffers above — never on the pt_render path.
+        int tracking = 0, editMaxHistory = 0;
+        unsigned char objectMap[pt::kObjectMapEntries * 32] = {0};
+        bool mapValid = false, mapTracked = false;
+        float4 *dObjectMap = nullptr;
 
         bool allocated() const
         {
-            return dGuides || dImage[0] || dImage[1] || dVariance || set[0].image || set[0].guides || set[1].image || set[1].guides;
+            return dGuides || dImage[0] || dImage[1] || dVariance || set[0].image || set[0].guides || set[1].image || set[1].guides || dObjectMap;
         }
         // frees whatever is allocated and nulls the pointers (the caller has made sure that nothing queued still uses them); the first error
         hipError_t release()
@@ -222,6 +233,7 @@ struct pt_renderer {
             };
             drop(dGuides);
             drop(dVariance);
+            drop(dObjectMap);
             for (float4 *&img : dImage) drop(img);
             for (DenoiseSet &s : set) {
                 drop(s.image);

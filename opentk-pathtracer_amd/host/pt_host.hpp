@@ -389,6 +389,25 @@ public:
         Check(pt_denoise_read_history(h_, s.image.data(), s.guides.data(), s.B, s.O), h_);
         return s;
     }
+    // object tracking for the temporal Denoise() calls that follow (Gui.cs:154-218: Upload + reset after an object edit): the history of an
+    // object that moved or was resized is found through its own motion, that of an object whose material changed is dropped for it alone;
+    // editMaxHistory (0..65535, 0 = maxHistory) caps the history count after such an edit.  No ClearDenoiseHistory() for object edits then.
+    void SetDenoiseTracking(bool enable = true, int editMaxHistory = 0) { Check(pt_denoise_set_object_tracking(h_, enable ? 1 : 0, editMaxHistory), h_); }
+    // the object map of the last Denoise(): 320 entries by guide id; tracked = the scene differed from the history's
+    struct ObjectMapEntry {
+        float A[3];
+        int32_t State; // PT_TRACK_KEEP / PT_TRACK_MOVED / PT_TRACK_DROP
+        float B[3];
+        int32_t Zero;
+    };
+    std::vector<ObjectMapEntry> DenoiseObjectMap(bool *tracked = nullptr) const
+    {
+        std::vector<ObjectMapEntry> map(PT_MAX_SPHERES + PT_MAX_CUBOIDS);
+        int t = 0;
+        Check(pt_denoise_read_object_map(h_, map.data(), &t), h_);
+        if (tracked) *tracked = t != 0;
+        return map;
+    }
     // lens mode for the Denoise() calls that follow, for a host that renders with the lens open (MainWindow.cs:189): guides from the pinhole
     // ray through the pixel's centre, and taps within cocScale times the lens's blur radius of both their ends taken on the luminance stop alone
     void SetDenoiseLens(bool enable = true, float cocScale = 1.0f) { Check(pt_denoise_set_lens(h_, enable ? 1 : 0, cocScale), h_); }

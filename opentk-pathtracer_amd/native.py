@@ -33,6 +33,7 @@ PT_MAX_SPHERES, PT_MAX_CUBOIDS = 256, 64  # first-hit ids: sphere i = i, cuboid 
 PT_ARITH_CONTRACT, PT_ARITH_REFERENCE = 0, 1  # pt_set_arithmetic, pt_atmosphere_set_arithmetic, pt_present_set_arithmetic
 PT_DENOISE_FIXED, PT_DENOISE_VARIANCE = 0, 1  # pt_denoise_set_mode
 PT_RAY_SAMPLE0, PT_RAY_PINHOLE = 0, 1  # pt_first_hit_set_ray
+PT_TRACK_KEEP, PT_TRACK_MOVED, PT_TRACK_DROP = 0, 1, 2  # states of the object map (pt_denoise_read_object_map)
 
 
 class NativeError(RuntimeError):
@@ -231,6 +232,8 @@ def load() -> C.CDLL:
         "pt_denoise_read_integrated": [vp, fp, C.c_size_t],
         "pt_denoise_read_history": [vp, fp, vp, fp, fp],
         "pt_denoise_set_lens": [vp, C.c_int, C.c_float],
+        "pt_denoise_set_object_tracking": [vp, C.c_int, C.c_int],
+        "pt_denoise_read_object_map": [vp, vp, ip],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -24,6 +24,9 @@ assert FIRST_HIT_DTYPE.itemsize == 32
 # one guide record of pt_denoise_read_guides (include/mi355pt.h): 32 bytes; id and t as in FIRST_HIT_DTYPE
 GUIDE_DTYPE = np.dtype([("pos", np.float32, 3), ("id", np.int32), ("normal", np.float32, 3), ("t", np.float32)])
 assert GUIDE_DTYPE.itemsize == 32
+# an entry of the object map (pt_denoise_read_object_map): history point = a * P + b per component, state = PT_TRACK_KEEP / MOVED / DROP
+OBJECT_MAP_DTYPE = np.dtype([("a", np.float32, 3), ("state", np.int32), ("b", np.float32, 3), ("zero", np.int32)])
+assert OBJECT_MAP_DTYPE.itemsize == 32
 
 
 class EnvironmentMap:
@@ -358,6 +361,20 @@ class PathTracer:
         check(self._lib.pt_denoise_read_history(self._h, image.ctypes.data_as(fp), guides.ctypes.data_as(C.c_void_p), B.ctypes.data_as(fp),
                                                 O.ctypes.data_as(fp)), self._h)
         return image, guides, B, O
+
+    def SetDenoiseTracking(self, enable: bool = True, edit_max_history: int = 0) -> None:
+        """pt_denoise_set_object_tracking: the temporal Denoise calls that follow compare the scene with the one their history was made of —
+        the history of an object that moved or was resized is found through that object's own motion, that of an object whose material
+        changed is dropped for that object only; edit_max_history (0..65535, 0 = max_history) caps the history count after such an edit."""
+        check(self._lib.pt_denoise_set_object_tracking(self._h, int(enable), edit_max_history), self._h)
+
+    def DenoiseObjectMap(self):
+        """pt_denoise_read_object_map: -> (the object map of the last Denoise as 320 entries of OBJECT_MAP_DTYPE, indexed by guide id;
+        tracked: True if the scene differed from the history's and the tracked kernel ran)."""
+        out = np.empty(native.PT_MAX_SPHERES + native.PT_MAX_CUBOIDS, dtype=OBJECT_MAP_DTYPE)
+        tracked = C.c_int()
+        check(self._lib.pt_denoise_read_object_map(self._h, out.ctypes.data_as(C.c_void_p), C.byref(tracked)), self._h)
+        return out, bool(tracked.value)
 
     def SetDenoiseLens(self, enable: bool = True, coc_scale: float = 1.0) -> None:
         """pt_denoise_set_lens: the Denoise calls that follow take their guides from the pinhole ray through the pixel's centre instead
