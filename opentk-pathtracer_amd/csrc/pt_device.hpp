@@ -83,18 +83,6 @@ PT_DEV v3 env_texel(const EnvRef &e, int face, int x, int y)
     return V(e.lut[t.x], e.lut[t.y], e.lut[t.z]);
 }
 
-PT_DEV void face_to_dir(int face, float sc, float tc, float &x, float &y, float &z)
-{
-    switch (face) {
-    case 0: x = 1.0f; y = -tc; z = -sc; break;
-    case 1: x = -1.0f; y = -tc; z = sc; break;
-    case 2: x = sc; y = 1.0f; z = tc; break;
-    case 3: x = sc; y = -1.0f; z = -tc; break;
-    case 4: x = sc; y = -tc; z = 1.0f; break;
-    default: x = -sc; y = -tc; z = -1.0f; break;
-    }
-}
-
 PT_DEV void dir_to_face(float x, float y, float z, int &face, float &sc, float &tc, float &ma)
 {
     float ax = f_abs(x), ay = f_abs(y), az = f_abs(z);
@@ -107,25 +95,46 @@ PT_DEV void dir_to_face(float x, float y, float z, int &face, float &sc, float &
     }
 }
 
-// texel (ix,iy), possibly one step outside `face` in one direction -> the texel across the seam
+// Texel (ix,iy) one step outside `face` -> (face, x, y) of the texel across the seam, in integers, exact for every size the API
+// accepts.  The centre of texel (x,y) of a face sits at in-face coordinates (2x+1-S, 2y+1-S) on the cube of half-width S, the face's
+// own axis at +-S (inverse of table 8.19).  A tap one step off has one in-face coordinate at +-(S+1); its neighbour is the border texel
+// of the face that coordinate points to: the old major axis drops to the outermost texel centre +-(S-1), the coordinate along the edge
+// is kept.  So the tap is written with S-1 on its own axis, +-(S+1) is the unique largest component, and table 8.19 in integers
+// returns the neighbour's lattice point; (c+S-1)/2 is its texel.  (The earlier rule re-projected the tap's centre through 3D in
+// binary32 and took floor: one texel off along the edge next to a face corner at some sizes from 3352 upwards, this rule's texel at
+// every border tap of every size below.)  Taps further out (NaN / inf / subnormal directions only, through the clamp in sample_env)
+// get a defined texel inside the cube through the same ties and the final clamp.  oracle/pt_oracle.c holds the same function.
+PT_DEV void env_wrapped_index(int S, int face, int ix, int iy, int &nface, int &nx, int &ny)
+{
+    const int a = 2 * ix + 1 - S, b = 2 * iy + 1 - S, m = S - 1;
+    int x, y, z, sc, tc;
+    switch (face) {
+    case 0: x = m; y = -b; z = -a; break;
+    case 1: x = -m; y = -b; z = a; break;
+    case 2: x = a; y = m; z = b; break;
+    case 3: x = a; y = -m; z = -b; break;
+    case 4: x = a; y = -b; z = m; break;
+    default: x = -a; y = -b; z = -m; break;
+    }
+    const int ax = x < 0 ? -x : x, ay = y < 0 ? -y : y, az = z < 0 ? -z : z;
+    if (az >= (ax > ay ? ax : ay)) {
+        nface = z < 0 ? 5 : 4; sc = z < 0 ? -x : x; tc = -y;
+    } else if (ax >= ay) {
+        nface = x < 0 ? 1 : 0; sc = x < 0 ? z : -z; tc = -y;
+    } else {
+        nface = y < 0 ? 3 : 2; sc = x; tc = y < 0 ? -z : z;
+    }
+    const int u = (sc + m) >> 1, v = (tc + m) >> 1; // sc + m is even for a texel centre; >> floors the off-lattice cases
+    nx = u < 0 ? 0 : (u > m ? m : u);
+    ny = v < 0 ? 0 : (v > m ? m : v);
+}
+
+// texel (ix,iy), possibly outside `face` -> the texel itself or the one across the seam
 PT_DEV v3 env_texel_wrapped(const EnvRef &e, int face, int ix, int iy)
 {
-    int S = e.size;
+    int S = e.size, nface, nx, ny;
     if (ix >= 0 && ix < S && iy >= 0 && iy < S) return env_texel(e, face, ix, iy);
-    float fs = (float)S;
-    float rfs = f_div_ieee(1.0f, fs); // uniform
-    float sc = ((float)ix + 0.5f) * rfs * 2.0f - 1.0f;
-    float tc = ((float)iy + 0.5f) * rfs * 2.0f - 1.0f;
-    float x, y, z, ma, nsc, ntc;
-    int nface;
-    face_to_dir(face, sc, tc, x, y, z);
-    dir_to_face(x, y, z, nface, nsc, ntc, ma);
-    float rma = f_rcp(ma);
-    float u = (nsc * rma * 0.5f + 0.5f) * fs;
-    float v = (ntc * rma * 0.5f + 0.5f) * fs;
-    int nx = (int)__builtin_floorf(u), ny = (int)__builtin_floorf(v);
-    nx = nx < 0 ? 0 : (nx > S - 1 ? S - 1 : nx);
-    ny = ny < 0 ? 0 : (ny > S - 1 ? S - 1 : ny);
+    env_wrapped_index(S, face, ix, iy, nface, nx, ny);
     return env_texel(e, nface, nx, ny);
 }
 
@@ -161,11 +170,6 @@ PT_DEV v3 sample_env(const EnvRef &e, v3 d)
         }
     } else {
         bool miss00 = offx0 && offy0, miss10 = offx1 && offy0, miss01 = offx0 && offy1, miss11 = offx1 && offy1;
-        v3 zero = V(0.0f, 0.0f, 0.0f);
-        t00 = miss00 ? zero : env_texel_wrapped(e, face, x0, y0);
-        t10 = miss10 ? zero : env_texel_wrapped(e, face, x1, y0);
-        t01 = miss01 ? zero : env_texel_wrapped(e, face, x0, y1);
-        t11 = miss11 ? zero : env_texel_wrapped(e, face, x1, y1);
         if (miss00 || miss10 || miss01 || miss11) {
             // cube corner: the missing tap's weight is shared equally by the three existing taps
             float a = (miss00 ? w00 : miss10 ? w10 : miss01 ? w01 : w11) * 0.333333343f;
@@ -174,6 +178,16 @@ PT_DEV v3 sample_env(const EnvRef &e, v3 d)
             w01 = miss01 ? 0.0f : w01 + a;
             w11 = miss11 ? 0.0f : w11 + a;
         }
+        // the same sum as below, one tap at a time: three running sums instead of twelve tap values
+        v3 zero = V(0.0f, 0.0f, 0.0f);
+        v3 t = miss00 ? zero : env_texel_wrapped(e, face, x0, y0);
+        v3 o = V(t.x * w00, t.y * w00, t.z * w00);
+        t = miss10 ? zero : env_texel_wrapped(e, face, x1, y0);
+        o = V(f_fma(t.x, w10, o.x), f_fma(t.y, w10, o.y), f_fma(t.z, w10, o.z));
+        t = miss01 ? zero : env_texel_wrapped(e, face, x0, y1);
+        o = V(f_fma(t.x, w01, o.x), f_fma(t.y, w01, o.y), f_fma(t.z, w01, o.z));
+        t = miss11 ? zero : env_texel_wrapped(e, face, x1, y1);
+        return V(f_fma(t.x, w11, o.x), f_fma(t.y, w11, o.y), f_fma(t.z, w11, o.z));
     }
     v3 o;
     o.x = f_fma(t11.x, w11, f_fma(t01.x, w01, f_fma(t10.x, w10, t00.x * w00)));

@@ -140,27 +140,9 @@ PT_HD void r_mat_vec(const float *m, float x, float y, float z, float w, float *
 
 #ifndef PT_REFERENCE_PRIMITIVES_ONLY
 // ---------------------------------------------------------------------------------------------- environment (compute.glsl:177)
-// texel (ix,iy), possibly one step outside `face` in one direction -> the texel across the seam (pt_device.hpp's, with 1 / ma exact)
-PT_DEV v3 env_texel_wrapped_ref(const EnvRef &e, int face, int ix, int iy)
-{
-    const int S = e.size;
-    if (ix >= 0 && ix < S && iy >= 0 && iy < S) return env_texel(e, face, ix, iy);
-    const float fs = (float)S;
-    const float rfs = 1.0f / fs;
-    const float sc = ((float)ix + 0.5f) * rfs * 2.0f - 1.0f;
-    const float tc = ((float)iy + 0.5f) * rfs * 2.0f - 1.0f;
-    float x, y, z, ma, nsc, ntc;
-    int nface;
-    face_to_dir(face, sc, tc, x, y, z);
-    dir_to_face(x, y, z, nface, nsc, ntc, ma);
-    const float rma = r_rcp(ma);
-    const float u = (nsc * rma * 0.5f + 0.5f) * fs;
-    const float v = (ntc * rma * 0.5f + 0.5f) * fs;
-    int nx = (int)__builtin_floorf(u), ny = (int)__builtin_floorf(v);
-    nx = nx < 0 ? 0 : (nx > S - 1 ? S - 1 : nx);
-    ny = ny < 0 ? 0 : (ny > S - 1 ? S - 1 : ny);
-    return env_texel(e, nface, nx, ny);
-}
+// texel (ix,iy), possibly outside `face` -> the texel itself or the one across the seam: pt_device.hpp's, the neighbour is integer arithmetic
+// and has no arithmetic choice in it
+PT_DEV v3 env_texel_wrapped_ref(const EnvRef &e, int face, int ix, int iy) { return env_texel_wrapped(e, face, ix, iy); }
 // texture(samplerCube, dir): LOD 0, LINEAR, seamless.  Without a cube-corner tap: two nested fused lerps, x first (llvmpipe's filter);
 // at a cube corner the missing tap's weight is shared by the other three, and the four weighted taps are summed unfused
 PT_DEV v3 sample_env_ref(const EnvRef &e, v3 d)

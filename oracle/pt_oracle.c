@@ -271,19 +271,6 @@ static rgb env_texel(const Ctx *c, int face, int x, int y)
     return o;
 }
 
-/* direction of the point (s,t) in [-1,1]^2 on `face` (inverse of table 8.19), not normalised */
-static void face_to_dir(int face, float sc, float tc, float *x, float *y, float *z)
-{
-    switch (face) {
-    case 0: *x = 1.0f;  *y = -tc;  *z = -sc;  break;
-    case 1: *x = -1.0f; *y = -tc;  *z = sc;   break;
-    case 2: *x = sc;    *y = 1.0f; *z = tc;   break;
-    case 3: *x = sc;    *y = -1.0f; *z = -tc; break;
-    case 4: *x = sc;    *y = -tc;  *z = 1.0f; break;
-    default: *x = -sc;  *y = -tc;  *z = -1.0f; break;
-    }
-}
-
 static void dir_to_face(float x, float y, float z, int *face, float *sc, float *tc, float *ma)
 {
     float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
@@ -292,27 +279,44 @@ static void dir_to_face(float x, float y, float z, int *face, float *sc, float *
     else                     { *face = y < 0.0f ? 3 : 2; *ma = ay; *sc = x; *tc = y < 0.0f ? -z : z; }
 }
 
-/* integer texel (ix,iy) possibly one step outside `face` in ONE direction -> texel on the neighbouring face */
+/* Texel (ix,iy) one step outside `face` -> (face, x, y) of the texel across the seam, in integers, exact for every size.
+ * Lattice: the centre of texel (x,y) of a face sits at in-face coordinates (2x+1-S, 2y+1-S) on the cube of half-width S, the face's
+ * own axis at +-S (inverse of table 8.19).  A tap one step off the face has one in-face coordinate at +-(S+1); its neighbour is the
+ * border texel of the face that coordinate points to: that axis becomes the new major axis, the old major axis drops to the outermost
+ * texel centre +-(S-1), the coordinate along the edge is kept.  So the tap is written with S-1 on its own axis, the overflowing
+ * +-(S+1) is the unique largest component, and table 8.19 in integers returns the neighbour's lattice point; (c+S-1)/2 is its texel.
+ * (The earlier rule re-projected the tap's centre through 3D in binary32 and took floor: one texel off along the edge next to a
+ * face corner at some sizes from 3352 upwards, the same texel as this rule at every border tap of every size below.)
+ * Taps further out (both coordinates off, or two steps off: only NaN / inf / subnormal directions reach them through the clamp in
+ * sample_env) get a defined texel inside the cube through the same ties (Z, X, Y) and the final clamp. */
+static void env_wrapped_index(int S, int face, int ix, int iy, int *nface, int *nx, int *ny)
+{
+    const int a = 2 * ix + 1 - S, b = 2 * iy + 1 - S, m = S - 1;
+    int x, y, z, sc, tc;
+    switch (face) {
+    case 0: x = m;   y = -b;  z = -a;  break;
+    case 1: x = -m;  y = -b;  z = a;   break;
+    case 2: x = a;   y = m;   z = b;   break;
+    case 3: x = a;   y = -m;  z = -b;  break;
+    case 4: x = a;   y = -b;  z = m;   break;
+    default: x = -a; y = -b;  z = -m;  break;
+    }
+    const int ax = x < 0 ? -x : x, ay = y < 0 ? -y : y, az = z < 0 ? -z : z;
+    if (az >= (ax > ay ? ax : ay)) { *nface = z < 0 ? 5 : 4; sc = z < 0 ? -x : x; tc = -y; }
+    else if (ax >= ay)             { *nface = x < 0 ? 1 : 0; sc = x < 0 ? z : -z; tc = -y; }
+    else                           { *nface = y < 0 ? 3 : 2; sc = x; tc = y < 0 ? -z : z; }
+    int u = (sc + m) >> 1, v = (tc + m) >> 1; /* sc + m is even for a texel centre; >> floors the off-lattice cases */
+    if (u < 0) u = 0; if (u > m) u = m;
+    if (v < 0) v = 0; if (v > m) v = m;
+    *nx = u; *ny = v;
+}
+
+/* integer texel (ix,iy), possibly outside `face` -> the texel itself or the one across the seam */
 static rgb env_texel_wrapped(const Ctx *c, int face, int ix, int iy)
 {
-    int S = c->envSize;
+    int S = c->envSize, nface, nx, ny;
     if (ix >= 0 && ix < S && iy >= 0 && iy < S) return env_texel(c, face, ix, iy);
-    /* texel centre in face coordinates, then re-project through 3D onto the neighbour face */
-    float fs = (float)S;
-    float rfs = 1.0f / fs; /* uniform */
-    float sc = ((float)ix + 0.5f) * rfs * 2.0f - 1.0f;
-    float tc = ((float)iy + 0.5f) * rfs * 2.0f - 1.0f;
-    float x, y, z, ma, nsc, ntc;
-    int nface;
-    face_to_dir(face, sc, tc, &x, &y, &z);
-    /* push the major axis below the overflowing one so the neighbour wins the selection */
-    dir_to_face(x, y, z, &nface, &nsc, &ntc, &ma);
-    float rma = f_rcp(ma);
-    float u = (nsc * rma * 0.5f + 0.5f) * fs;
-    float v = (ntc * rma * 0.5f + 0.5f) * fs;
-    int nx = (int)floorf(u), ny = (int)floorf(v);
-    if (nx < 0) nx = 0; if (nx > S - 1) nx = S - 1;
-    if (ny < 0) ny = 0; if (ny > S - 1) ny = S - 1;
+    env_wrapped_index(S, face, ix, iy, &nface, &nx, &ny);
     return env_texel(c, nface, nx, ny);
 }
 
@@ -859,6 +863,29 @@ PTO_API void pto_sample_env(const void *env, int size, int format, const float *
     fill_lut(c.srgbLut);
     rgb o = sample_env(&c, V(dir[0], dir[1], dir[2]));
     rgb_out[0] = o.r; rgb_out[1] = o.g; rgb_out[2] = o.b;
+}
+/* n directions (3 floats each) -> n rgb triples: pto_sample_env over an array, the sRGB table built once */
+PTO_API void pto_sample_env_n(const void *env, int size, int format, const float *dirs, int n, float *rgb_out)
+{
+    Ctx c;
+    memset(&c, 0, sizeof c);
+    c.env = env; c.envSize = size; c.envFormat = format;
+    fill_lut(c.srgbLut);
+    for (int i = 0; i < n; i++) {
+        rgb o = sample_env(&c, V(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+        rgb_out[3 * i] = o.r; rgb_out[3 * i + 1] = o.g; rgb_out[3 * i + 2] = o.b;
+    }
+}
+/* The seam rule alone: (face, x, y) of all 24*S off-face border taps of one size through the code env_texel_wrapped runs.
+ * out[((face * 4 + edge) * S + p) * 3 + {0,1,2}]; edge 0: tap (-1, p), 1: (S, p), 2: (p, -1), 3: (p, S). */
+PTO_API void pto_env_wrapped_index(int size, int *out)
+{
+    for (int face = 0; face < 6; face++)
+        for (int edge = 0; edge < 4; edge++)
+            for (int p = 0; p < size; p++) {
+                int *o = out + (((size_t)face * 4 + edge) * size + p) * 3;
+                env_wrapped_index(size, face, edge == 0 ? -1 : edge == 1 ? size : p, edge == 2 ? -1 : edge == 3 ? size : p, o, o + 1, o + 2);
+            }
 }
 PTO_API float pto_srgb_to_linear(int v) { return srgb_to_linear(v); }
 PTO_API float pto_pow5(float x) { return f_pow5(x); }

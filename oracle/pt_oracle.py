@@ -404,6 +404,23 @@ class Oracle:
             assert self._lut.size == 256
             self.lib.pto_set_srgb_lut(_ptr(self._lut))
 
+    def sample_env_n(self, env_faces, directions):
+        """sample_env over an (n, 3) array of directions -> (n, 3)"""
+        env = np.ascontiguousarray(env_faces)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        out = np.zeros((len(d), 3), np.float32)
+        self.lib.pto_sample_env_n.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, C.c_int, _fp]
+        self.lib.pto_sample_env_n(env.ctypes.data_as(C.c_void_p), env.shape[1], 0 if env.dtype == np.float32 else 1, _ptr(d), len(d), _ptr(out))
+        return out
+
+    def env_wrapped_index(self, size):
+        """(6, 4, size, 3) int32: (face, x, y) of every off-face border tap of one size, through the code env_texel_wrapped runs
+        (edge 0: tap (-1, p), 1: (size, p), 2: (p, -1), 3: (p, size))"""
+        out = np.zeros((6, 4, size, 3), np.int32)
+        self.lib.pto_env_wrapped_index.argtypes = [C.c_int, C.c_void_p]
+        self.lib.pto_env_wrapped_index(size, out.ctypes.data_as(C.c_void_p))
+        return out
+
     def sample_env(self, env_faces, direction):
         env = np.ascontiguousarray(env_faces)
         d = np.ascontiguousarray(direction, np.float32)
