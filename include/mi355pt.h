@@ -485,6 +485,41 @@ PT_API int pt_denoise_read_object_map(pt_handle h, void *dst_320x32_bytes, int *
  * force then.  Defaults 0, 1.  With enable = 0 pt_denoise_render is bit for bit what it was.  Scope as for pt_denoise_set_params. */
 PT_API int pt_denoise_set_lens(pt_handle h, int enable, float coc_scale);
 
+/* Temporal moments (the temporal-moments half of SVGF, Schied et al. 2017): a per-pixel noise estimate measured
+ * ACROSS frames instead of across neighbours, for a host that keeps the denoised image on screen while the image of MainWindow.cs:49-63
+ * converges behind it.  The spatial estimate V0 of PT_DENOISE_VARIANCE counts image detail inside one id (reflections, refractions) as
+ * noise, so it stops falling while the true noise still does.  With the switch on, every pt_denoise_render OBSERVES the image: the
+ * handle keeps a MOMENT SET — per pixel the luminance of the last observation and the running sum of squares M2, per handle the
+ * observation count K and the sample count of the last observation — updated by the weighted Welford rule from the image alone (the
+ * samples since the last look enter as their block mean, so a host may look every frame or every few), and forgotten (K = 0) when the
+ * reset epoch or spp changes, the frame index goes back, or the handle is resized or re-tiled.  A render that finds the image as the
+ * last observation saw it (or empty) counts nothing twice.  Vm = the variance of the tone-compressed luminance of the image as it
+ * stands, M2 / (K - 1) / n carried through the tone curve; 0 on a miss and while K < 2.  In PT_DENOISE_VARIANCE with iterations > 0, the
+ * temporal stage off and K >= 2, pass 0 reads var_0 = ((K - 1) Vt + prior_samples V0) / (K - 1 + prior_samples) in place of V0, Vt = the
+ * mean of Vm over the pixels of the same id in the 3x3 window; pt_denoise_read_variance still returns V0.  In every other case the
+ * filter's result is bit for bit what it is with the switch off, and the observations and the two read-outs below work all the same.
+ * Limit: with the temporal stage on the passes filter the integrated image, whose noise is not the accumulation image's, so Vm is
+ * measured and not used.  Reads the image's RGB only; touches neither the image, the frame counter nor anything pt_render reads. */
+
+/* Switch of the pt_denoise_render calls that follow — a GUI toggle's setter, like those MainWindow.cs:49-63 drives; the result is shown
+ * through ScreenEffect.cs:29-37; what is queued already keeps the values it was issued under.  enable: 0 or 1, anything else
+ * PT_E_BAD_ARGUMENT; prior_samples 1..65535 (how many observations the spatial estimate is worth in the blend), outside that
+ * PT_E_OUT_OF_RANGE; the previous values stay in force then.  Defaults 0, 32.  With enable = 0 pt_denoise_render is bit for bit what it
+ * was, observes nothing and allocates nothing; the moment set stays as it is.  Scope as for pt_denoise_set_params. */
+PT_API int pt_denoise_set_moments(pt_handle h, int enable, int prior_samples);
+/* The noise map Vm of the last pt_denoise_render — how far the image of MainWindow.cs:49-63 still is from converged, before it goes to
+ * ScreenEffect.cs:29-37 — one float per pixel (0 on a miss), rows like the image: blocks; row_pitch_bytes >= width*4, 0 = tightly
+ * packed.  Unlike pt_denoise_read_variance's map this one does become flat where the image has detail.  PT_E_BAD_ARGUMENT when the last
+ * render ran with the switch off, when fewer than two observations exist, when nothing was rendered since the last (re)size /
+ * (re)tiling, for dst == NULL or a pitch smaller than a row. */
+PT_API int pt_denoise_read_noise(pt_handle h, float *dst, size_t row_pitch_bytes);
+/* The convergence figure of the image of MainWindow.cs:49-63 (what a host compares with a threshold to stop denoising, or rendering,
+ * instead of showing ScreenEffect.cs:29-37 a filtered image for ever): *out_mean_variance = the mean of Vm over the pixels with id >= 0
+ * (0 if there is none), *out_observations = K, *out_hit_pixels = that pixel count.  A device reduction forms one binary32 sum and one
+ * count per 256 pixels; the host adds them in index order in double.  Blocks.  Any pointer may be NULL.  PT_E_BAD_ARGUMENT in the first
+ * three cases of pt_denoise_read_noise. */
+PT_API int pt_denoise_noise_level(pt_handle h, float *out_mean_variance, int *out_observations, int *out_hit_pixels);
+
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);
 PT_API int pt_device_count(void);

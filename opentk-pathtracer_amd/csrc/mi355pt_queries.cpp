@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 using ptimpl::bind_device;
 using ptimpl::ensure_rgba8;
@@ -30,6 +31,8 @@ int free_denoise(pt_handle h)
     d.varianceValid = false;
     d.integratedValid = d.historyUsed = false;
     d.mapValid = d.mapTracked = false;
+    d.momentsK = 0; // (the moment set belongs to a size and a tiling)
+    d.noiseValid = d.blended = false;
     for (pt_renderer::DenoiseSet &set : d.set) set.valid = false;
     if (!d.allocated()) return PT_OK;
     PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_denoise_render may still write them)
@@ -220,6 +223,49 @@ static bool denoise_object_map(const pt_renderer::DenoiseSet &hist, const unsign
     return ptmap::build(hist.scene, hist.numSpheres, hist.numCuboids, scene, ns, nc, map);
 }
 
+// The moment set of pt_denoise_set_moments (pt_denoise_moments.hip) is forgotten when it was made in another reset epoch,
+// under another spp, or of more samples than the image holds now (a resize or re-tiling forgets it in free_denoise)
+static bool moments_forgotten(pt_handle h)
+{
+    const pt_renderer::Denoiser &d = h->denoise;
+    return d.momentsK > 0 && (d.momentsEpoch != h->resetEpoch || d.momentsSpp != h->spp || (long long)h->frame * h->spp < d.momentsN);
+}
+
+// Stage M of a full render with the switch on: looks at the accumulation image — an observation unless it holds no sample (n = 0) or
+// what the last observation saw (n = nPrev) — and leaves Vm in dNoise.  n, nPrev and n - nPrev are converted to binary32 here.
+static int denoise_observe(pt_handle h, const float4 *guides)
+{
+    pt_renderer::Denoiser &d = h->denoise;
+    const size_t pixels = h->tilePixels();
+    if (!d.dMoments) PT_HIP(h, hipMalloc((void **)&d.dMoments, pixels * sizeof(float2)));
+    if (!d.dNoise) PT_HIP(h, hipMalloc((void **)&d.dNoise, pixels * sizeof(float)));
+    if (!d.dVar0) PT_HIP(h, hipMalloc((void **)&d.dVar0, pixels * sizeof(float)));
+    if (moments_forgotten(h)) d.momentsK = 0;
+    const long long n = (long long)h->frame * h->spp;
+    const bool observe = n != 0 && !(d.momentsK > 0 && n == d.momentsN);
+    pt::MomentsArgs m;
+    m.colIn = h->accum();
+    m.guides = guides;
+    m.state = d.dMoments;
+    m.noise = d.dNoise;
+    m.pixels = pixels;
+    m.observe = !observe ? 0 : d.momentsK == 0 ? 1 : 2;
+    m.nf = (float)n;
+    m.npf = (float)d.momentsN;
+    m.w = (float)(n - d.momentsN);
+    if (observe) {
+        d.momentsK += 1;
+        d.momentsN = n;
+        d.momentsSpp = h->spp;
+        d.momentsEpoch = h->resetEpoch;
+    }
+    m.estimate = d.momentsK >= 2;
+    m.km1 = (float)(d.momentsK - 1);
+    PT_HIP(h, pt::launch_moments(m, h->stream));
+    d.noiseValid = true;
+    return PT_OK;
+}
+
 // stage kDenoiseAll: everything; -1: the guides only; kDenoiseStageV: stage V of the variance mode only; kDenoiseStageT: the temporal
 // kernel only; i >= 0: pass i only (pt_debug_denoise_stage, for timing)
 constexpr int kDenoiseStageV = -2, kDenoiseAll = -3, kDenoiseStageT = -4;
@@ -258,6 +304,11 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
         first_hit_args(h, a, guide_frame_index);
         PT_HIP(h, pt::launch_guides(a, guides, lens, h->stream));
         if (stage == -1) return PT_OK;
+    }
+    if (stage == kDenoiseAll) {
+        d.noiseValid = d.blended = false;
+        if (d.moments)
+            if (int rc = denoise_observe(h, guides)) return rc;
     }
     if (temporal && (stage == kDenoiseAll || stage == kDenoiseStageT)) {
         pt::TemporalArgs t;
@@ -314,6 +365,22 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
         v.height = h->rows;
         PT_HIP(h, pt::launch_variance(v, h->stream));
     }
+    // stage B: the measured variance blended with V0 into var_0, which pass 0 reads in place of V0 (a timing stage reads what the last
+    // full render left).  Not with the temporal stage on: the integrated image's noise is not the accumulation image's
+    if (stage == kDenoiseAll && d.noiseValid && variance && n > 0 && !temporal && d.momentsK >= 2) {
+        pt::MomentsBlendArgs b;
+        b.noise = d.dNoise;
+        b.guides = guides;
+        b.v0 = d.dVariance;
+        b.var0 = d.dVar0;
+        b.width = h->width;
+        b.height = h->rows;
+        b.km1 = (float)(d.momentsK - 1);
+        b.k0 = (float)d.priorSamples;
+        PT_HIP(h, pt::launch_moments_blend(b, h->stream));
+        d.blended = true;
+    }
+    const bool blended = d.blended && variance && !temporal && d.dVar0;
     for (int i = 0; i < n && stage != kDenoiseStageV; i++) {
         if (stage >= 0 && i != stage) continue;
         pt::AtrousArgs t;
@@ -329,7 +396,7 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
         t.variance = variance;
         t.invSigma = variance ? 0.0f : 1.0f / (d.sigmaColor * std::ldexp(1.0f, -i));
         t.k2 = variance ? d.sigmaVariance * d.sigmaVariance : 0.0f;
-        t.varIn = variance && i == 0 ? d.dVariance : nullptr;
+        t.varIn = variance && i == 0 ? (blended ? d.dVar0 : d.dVariance) : nullptr;
         t.last = variance && i == n - 1;
         t.lens = cocK > 0.0f; // (lens mode with cocK = 0: the pinhole guides under the tap rules of lens = 0)
         t.cocK = cocK;
@@ -496,6 +563,59 @@ PT_API int pt_denoise_read_history(pt_handle h, float *image, void *guides, floa
     return PT_OK;
 }
 
+PT_API int pt_denoise_set_moments(pt_handle h, int enable, int prior_samples)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    if (enable != 0 && enable != 1) return fail(h, PT_E_BAD_ARGUMENT, "enable must be 0 or 1");
+    if (prior_samples < 1 || prior_samples > 65535) return fail(h, PT_E_OUT_OF_RANGE, "prior_samples 1..65535");
+    h->denoise.moments = enable; // (read by the next pt_denoise_render; what is queued already took its values)
+    h->denoise.priorSamples = prior_samples;
+    return PT_OK;
+}
+
+// the last pt_denoise_render left a noise map of at least two observations of the image as it still stands
+static int denoise_noise_ready(pt_handle h)
+{
+    if (int rc = denoise_rendered(h)) return rc;
+    if (!h->denoise.noiseValid) return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render ran with pt_denoise_set_moments off");
+    if (moments_forgotten(h)) h->denoise.momentsK = 0;
+    if (h->denoise.momentsK < 2) return fail(h, PT_E_BAD_ARGUMENT, "fewer than two observations of the image (pt_denoise_render with pt_denoise_set_moments on)");
+    return PT_OK;
+}
+
+PT_API int pt_denoise_read_noise(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_noise_ready(h)) return rc;
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->denoise.dNoise, 4);
+}
+
+PT_API int pt_denoise_noise_level(pt_handle h, float *out_mean_variance, int *out_observations, int *out_hit_pixels)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_noise_ready(h)) return rc;
+    pt_renderer::Denoiser &d = h->denoise;
+    const size_t pixels = h->tilePixels(), blocks = (pixels + 255) / 256;
+    if (!d.dNoisePartial) PT_HIP(h, hipMalloc((void **)&d.dNoisePartial, blocks * sizeof(float2)));
+    PT_HIP(h, pt::launch_moments_level(d.dNoise, d.integratedValid ? d.set[d.current].guides : d.dGuides, d.dNoisePartial, pixels, h->stream));
+    std::vector<float2> partial(blocks);
+    PT_HIP(h, hipMemcpyAsync(partial.data(), d.dNoisePartial, blocks * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(h, hipStreamSynchronize(h->stream));
+    double sum = 0.0;
+    long long count = 0;
+    for (const float2 &p : partial) { // (in index order)
+        int c;
+        std::memcpy(&c, &p.y, sizeof c);
+        sum += (double)p.x;
+        count += c;
+    }
+    if (out_mean_variance) *out_mean_variance = count > 0 ? (float)(sum / (double)count) : 0.0f;
+    if (out_observations) *out_observations = d.momentsK;
+    if (out_hit_pixels) *out_hit_pixels = (int)count;
+    return PT_OK;
+}
+
 PT_API int pt_denoise_device_ptr(pt_handle h, void **out, size_t *bytes)
 {
     PT_CHECK_HANDLE(h);
@@ -534,6 +654,16 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_denoise_stage(pt_
     if (h->denoise.integratedValid != (h->denoise.temporal != 0))
         return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render ran with another setting of pt_denoise_set_temporal");
     return denoise_run(h, guide_frame_index, stage);
+}
+
+// Test aid (not declared in the public header): var_0 of the last pt_denoise_render, what pass 0 read in place of V0 — one float per
+// pixel, rows like the image; PT_E_BAD_ARGUMENT when that render did not run stage B (pt_denoise_set_moments).
+extern "C" __attribute__((visibility("default"))) int pt_debug_denoise_read_var0(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    if (!h->denoise.blended) return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render did not blend the measured variance into pass 0's");
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->denoise.dVar0, 4);
 }
 
 } // extern "C"

@@ -286,6 +286,34 @@ hipError_t launch_temporal(const TemporalArgs &a, hipStream_t stream);
 constexpr int kObjectMapEntries = 320; // PT_MAX_SPHERES + PT_MAX_CUBOIDS
 constexpr int kTrackKeep = 0, kTrackMoved = 1, kTrackDrop = 2;
 hipError_t launch_temporal_tracked(const TemporalArgs &a, const float4 *objectMap, hipStream_t stream);
+// the temporal moments (pt_denoise_set_moments; pt_denoise_moments.hip).  Stage M: one observation of colIn's luminance l
+// into state = (lprev, M2) per pixel, and noise = Vm, the variance of u measured across the observations (0 where the guide id is -1)
+struct MomentsArgs {
+    const float4 *colIn;  // the accumulation image; alpha is not read
+    const float4 *guides; // word 3 of a record's first half: the id
+    float2 *state;        // pixels x (lprev, M2)
+    float *noise;         // pixels floats
+    size_t pixels;
+    int observe;          // 0: no observation (state is read only), 1: the first one (M2 = 0; state is not read), 2: the Welford update
+    int estimate;         // K >= 2 counting this observation: Vm is formed, else 0
+    float nf, npf, w;     // (float)n, (float)nPrev, (float)(n - nPrev), converted by the host; npf and w are read by observe = 2 only
+    float km1;            // (float)(K - 1), K counting this observation; read where estimate is set
+};
+hipError_t launch_moments(const MomentsArgs &a, hipStream_t stream);
+// stage B: var0 = ((km1 Vt) + (k0 v0)) / (km1 + k0), Vt = the mean of noise over the pixels of the centre's id in its 3x3 window;
+// var0 = v0 where the id is -1
+struct MomentsBlendArgs {
+    const float *noise;   // Vm
+    const float4 *guides;
+    const float *v0;      // stage V's estimate
+    float *var0;          // width x height floats, compact rows
+    int width, height;
+    float km1, k0;        // (float)(K - 1), (float)prior_samples
+};
+hipError_t launch_moments_blend(const MomentsBlendArgs &a, hipStream_t stream);
+// pt_denoise_noise_level: partial[i] = (binary32 sum of noise over the pixels with id >= 0 among pixels 256 i .. 256 i + 255, their count
+// as int bits); partial holds (pixels + 255) / 256 entries
+hipError_t launch_moments_level(const float *noise, const float4 *guides, float2 *partial, size_t pixels, hipStream_t stream);
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 // the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);

@@ -215,10 +215,24 @@ struct pt_renderer {
         unsigned char objectMap[pt::kObjectMapEntries * 32] = {0};
         bool mapValid = false, mapTracked = false;
         float4 *dObjectMap = nullptr;
+        // Temporal moments (pt_denoise_set_moments; pt_denoise_moments.hip): the moment set — dMoments = (lprev, M2) per pixel, momentsK =
+        // the observation count K, momentsN = the sample count nPrev of the last observation, momentsSpp / momentsEpoch = the spp and the
+        // reset epoch it was made under (K = 0: nothing observed, the other three are not read).  dNoise = Vm and dVar0 = stage B's var_0,
+        // rows x width floats each; all three allocated by the first pt_denoise_render with the switch on and freed with the buffers
+        // above — never on the pt_render path; dNoisePartial = the (sum, count) per 256 pixels of pt_denoise_noise_level, allocated by its
+        // first call.  noiseValid: the last pt_denoise_render ran stage M; blended: ... and stage B, so pass 0 read dVar0.
+        int moments = 0, priorSamples = 32;
+        float2 *dMoments = nullptr, *dNoisePartial = nullptr;
+        float *dNoise = nullptr, *dVar0 = nullptr;
+        int momentsK = 0, momentsSpp = 0;
+        long long momentsN = 0;
+        unsigned long long momentsEpoch = 0;
+        bool noiseValid = false, blended = false;
 
         bool allocated() const
         {
-            return dGuides || dImage[0] || dImage[1] || dVariance || set[0].image || set[0].guides || set[1].image || set[1].guides || dObjectMap;
+            return dGuides || dImage[0] || dImage[1] || dVariance || set[0].image || set[0].guides || set[1].image || set[1].guides || dObjectMap ||
+                   dMoments || dNoisePartial || dNoise || dVar0;
         }
         // frees whatever is allocated and nulls the pointers (the caller has made sure that nothing queued still uses them); the first error
         hipError_t release()
@@ -234,6 +248,10 @@ struct pt_renderer {
             drop(dGuides);
             drop(dVariance);
             drop(dObjectMap);
+            drop(dMoments);
+            drop(dNoisePartial);
+            drop(dNoise);
+            drop(dVar0);
             for (float4 *&img : dImage) drop(img);
             for (DenoiseSet &s : set) {
                 drop(s.image);

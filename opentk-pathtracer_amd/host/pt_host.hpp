@@ -411,6 +411,23 @@ public:
     // lens mode for the Denoise() calls that follow, for a host that renders with the lens open (MainWindow.cs:189): guides from the pinhole
     // ray through the pixel's centre, and taps within cocScale times the lens's blur radius of both their ends taken on the luminance stop alone
     void SetDenoiseLens(bool enable = true, float cocScale = 1.0f) { Check(pt_denoise_set_lens(h_, enable ? 1 : 0, cocScale), h_); }
+    // temporal moments for the Denoise() calls that follow: each one observes the image, and from the second observation on
+    // PT_DENOISE_VARIANCE blends the variance measured across frames with the spatial estimate, worth priorSamples (1..65535) observations
+    void SetDenoiseMoments(bool enable = true, int priorSamples = 32) { Check(pt_denoise_set_moments(h_, enable ? 1 : 0, priorSamples), h_); }
+    // the noise map of the last Denoise() with the moments on: one float per pixel, row 0 = bottom (needs two observations)
+    std::vector<float> DenoiseNoise() const
+    {
+        std::vector<float> noise((size_t)width_ * height_);
+        Check(pt_denoise_read_noise(h_, noise.data(), 0), h_);
+        return noise;
+    }
+    // its mean over the pixels that hit an object — the convergence figure; observations / hitPixels may be null
+    float DenoiseNoiseLevel(int *observations = nullptr, int *hitPixels = nullptr) const
+    {
+        float mean = 0.0f;
+        Check(pt_denoise_noise_level(h_, &mean, observations, hitPixels), h_);
+        return mean;
+    }
     // ScreenEffect.Render (src/Render/ScreenEffect.cs:29-37) of the last Denoise() instead of `Result`
     std::vector<uint8_t> PresentDenoised() const
     {

@@ -382,6 +382,26 @@ class PathTracer:
         its ends (coc_scale 0: pinhole guides, the usual tap rules).  For a host that renders with the lens open."""
         check(self._lib.pt_denoise_set_lens(self._h, int(enable), coc_scale), self._h)
 
+    def SetDenoiseMoments(self, enable: bool = True, prior_samples: int = 32) -> None:
+        """pt_denoise_set_moments: the Denoise calls that follow observe the image and keep per-pixel moments across frames; from the
+        second observation on, PT_DENOISE_VARIANCE blends the variance measured that way with the spatial estimate, which counts as
+        prior_samples (1..65535) observations."""
+        check(self._lib.pt_denoise_set_moments(self._h, int(enable), prior_samples), self._h)
+
+    def DenoiseNoise(self) -> np.ndarray:
+        """pt_denoise_read_noise: the noise map Vm of the last Denoise with the moments on (variance of the tone-compressed luminance of
+        the image as it stands, measured across frames) as (rows, Width) float32; needs two observations."""
+        out = np.empty((self.rows, self.Width), dtype=np.float32)
+        check(self._lib.pt_denoise_read_noise(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
+        return out
+
+    def DenoiseNoiseLevel(self):
+        """pt_denoise_noise_level: -> (the mean of Vm over the pixels with id >= 0, the observation count K, that pixel count): the
+        convergence figure a host compares with a threshold."""
+        mean, k, hit = C.c_float(), C.c_int(), C.c_int()
+        check(self._lib.pt_denoise_noise_level(self._h, C.byref(mean), C.byref(k), C.byref(hit)), self._h)
+        return float(mean.value), int(k.value), int(hit.value)
+
     def PresentDenoised(self) -> np.ndarray:
         """pt_denoise_present_rgba8: the result of the last Denoise through the tone map Present applies, as (rows, Width, 4) uint8."""
         out = np.empty((self.rows, self.Width, 4), dtype=np.uint8)
