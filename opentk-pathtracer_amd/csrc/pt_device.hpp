@@ -209,7 +209,14 @@ PT_DEV v3 cuboid_normal(v3 mn, v3 mx, v3 p)
     n.x = f_sign(cs.x) * f_step(f_abs(f_abs(cs.x) - half.x), EPSILON);
     n.y = f_sign(cs.y) * f_step(f_abs(f_abs(cs.y) - half.y), EPSILON);
     n.z = f_sign(cs.z) * f_step(f_abs(f_abs(cs.z) - half.z), EPSILON);
-    return v_normalize(n);
+    // normalize(n) = n * f_rsqrt(dot(n, n)), the factor selected instead of computed.  Every component of n is -1, -0, +0 or +1 for
+    // every input (f_sign of a NaN is 0, f_step returns 0 or 1), so q below is exactly 0, 1, 2 or 3 and f_rsqrt(q) is one of four known
+    // values (f_rsqrt(0) = +inf: a hit on no face keeps its NaN normal).  Three compares and selects in place of the Newton sequence,
+    // which the wavefront issued in every iteration in which some lane hit a cuboid.
+    const float q = v_dot(n, n);
+    const float s = q == 1.0f ? __uint_as_float(RSQRT_1_BITS)
+                              : (q == 2.0f ? __uint_as_float(RSQRT_2_BITS) : (q == 3.0f ? __uint_as_float(RSQRT_3_BITS) : __builtin_inff()));
+    return v_scale(n, s);
 }
 
 PT_DEV Material load_material(const float4 *m)
@@ -807,7 +814,9 @@ PT_DEV float bsdf(v3 &ro, v3 &rd, const Hit &h, bool &isRefractive, uint32_t &se
 
 // One iteration of Radiance's bounce loop (compute.glsl:140-180) for one path.  Returns true when the path
 // continues (hit, survived Russian roulette), false when it ended (miss -> environment, or roulette kill).
-template <bool MASKED, bool MATLDS, bool GRID = false, bool SHARE = false>
+// GATES: the wave-uniform gates around Beer's law (below).  The spp > 1 kernel with materials in device memory and no grid is at its
+// register limit and pays for them with a scratch reload, so it alone keeps the ungated form.
+template <bool MASKED, bool MATLDS, bool GRID = false, bool SHARE = false, bool GATES = true>
 PT_DEV bool bounce_step_t(const SceneLds &sc, int ns, int nc, const EnvRef &env, v3 &ro, v3 &rd, v3 &throughput, v3 &rad,
                           uint32_t &seed, const unsigned long long *masks, float &walkFrom PROF_PARAM)
 {
@@ -820,9 +829,27 @@ PT_DEV bool bounce_step_t(const SceneLds &sc, int ns, int nc, const EnvRef &env,
         PROF_BEGIN
         if (h.fromInside) { // Beer's law, compute.glsl:145-149
             h.normal = v_neg(h.normal);
-            throughput.x *= pt_exp<SHARE>(-h.m.absorbance.x * h.T);
-            throughput.y *= pt_exp<SHARE>(-h.m.absorbance.y * h.T);
-            throughput.z *= pt_exp<SHARE>(-h.m.absorbance.z * h.T);
+            // A wavefront pays for three exponentials whenever one lane is here, so two wave-uniform gates (ballots over the lanes in
+            // this region) issue only what those lanes' absorbances need.  Per lane the operations are the ones written in the last
+            // branch; the gates only skip or share results that are bit-for-bit the same:
+            //   none  every lane's absorbance is (+-0, +-0, +-0).  T of a hit is finite (ray_trace_t: an accepted t1 / t2 passed its
+            //         comparisons, the cuboid's are clamped to +-FLOAT_MAX, a sphere's overflow only through a NaN square root, which
+            //         fails them), so -a * T is -0 or +0; pt_exp of either zero is exactly 1.0f (n = +-0, r = +-0, p * 0 + r + 1 = 1,
+            //         times 2^0 twice), and t * 1.0f keeps every bit of a finite, infinite or quiet-NaN t.  Nothing is issued.
+            //   one   every lane has three channels of equal bits: equal operands give equal results, one pt_exp serves all three.
+            //   three otherwise.
+            const uint32_t ax = __float_as_uint(h.m.absorbance.x), ay = __float_as_uint(h.m.absorbance.y), az = __float_as_uint(h.m.absorbance.z);
+            if (GATES && __ballot(((ax | ay | az) & 0x7fffffffu) != 0u) == 0ull) {
+            } else if (GATES && __ballot((ax != ay) | (ax != az)) == 0ull) {
+                const float t = pt_exp<SHARE>(-h.m.absorbance.x * h.T);
+                throughput.x *= t;
+                throughput.y *= t;
+                throughput.z *= t;
+            } else {
+                throughput.x *= pt_exp<SHARE>(-h.m.absorbance.x * h.T);
+                throughput.y *= pt_exp<SHARE>(-h.m.absorbance.y * h.T);
+                throughput.z *= pt_exp<SHARE>(-h.m.absorbance.z * h.T);
+            }
         }
         PROF_MARK(4) // Beer
         bool isRefractive;

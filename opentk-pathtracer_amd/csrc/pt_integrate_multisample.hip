@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256, 5) void pt_integrate_multisample_kernel(const 
                 bool tcont = false;
                 float walkFresh = -1.0f; // (the batch pass never walks the grid: a local, not a register carried round the main loop)
                 if (valid) {
-                    if (0 < a.rayDepth) tcont = bounce_step_t<true, MATLDS>(sc, a.numSpheres, a.numCuboids, env, to, td, tthr, trad, tseed, masks, walkFresh PROF_DUMMY);
+                    if (0 < a.rayDepth) tcont = bounce_step_t<true, MATLDS, false, false, (MATLDS || GRID)>(sc, a.numSpheres, a.numCuboids, env, to, td, tthr, trad, tseed, masks, walkFresh PROF_DUMMY);
                     if (1 >= a.rayDepth) tcont = false;
                 }
                 // 1. paths that continue go to the ring
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256, 5) void pt_integrate_multisample_kernel(const 
         bool wantPark = false;
         const bool trace = active && !pending; // (one divergent region around the bounce, as in the persistent kernel)
         bool cont = false;
-        if (trace && c_bounce() < a.rayDepth) cont = bounce_step_t<false, MATLDS, GRID, (MATLDS && !GRID)>(sc, a.numSpheres, a.numCuboids, env, ro, rd, throughput, rad, seed, nullptr, walkFrom PROF_DUMMY);
+        if (trace && c_bounce() < a.rayDepth) cont = bounce_step_t<false, MATLDS, GRID, (MATLDS && !GRID), (MATLDS || GRID)>(sc, a.numSpheres, a.numCuboids, env, ro, rd, throughput, rad, seed, nullptr, walkFrom PROF_DUMMY);
         if (trace) {
             const bool sliced = GRID && walkFrom >= 0.0f; // (the grid walk of this bounce continues in the next iteration: pt_device.hpp, WALK SLICES)
             if (!sliced) counters++; // bounce++ (< 4096 by the ABI's ray_depth limit: no carry into the sample field)

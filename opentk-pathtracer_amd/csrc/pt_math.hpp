@@ -19,7 +19,9 @@
 
 namespace pt {
 
+#ifndef PT_DEV // (a host-compiled probe of these sequences defines it as __host__ __device__ inline)
 #define PT_DEV __device__ __forceinline__
+#endif
 
 constexpr float FLOAT_MAX = 3.4028235e+38f;  // compute.glsl:2
 constexpr float FLOAT_MIN = -3.4028235e+38f; // compute.glsl:3
@@ -55,6 +57,9 @@ PT_DEV float f_rsqrt(float x)
     if (x < 1.17549435e-38f) y = x < 0.0f ? __builtin_nanf("") : __builtin_inff();
     return y;
 }
+// f_rsqrt(1.0f), f_rsqrt(2.0f), f_rsqrt(3.0f): the bits that sequence returns (not the correctly rounded values: f_rsqrt(1) is one ulp
+// below 1).  cuboid_normal selects among them; tests/test_bounce_regions_cpu.py runs the sequence on the host and holds them to it.
+constexpr uint32_t RSQRT_1_BITS = 0x3F7FFFFFu, RSQRT_2_BITS = 0x3F3504F4u, RSQRT_3_BITS = 0x3F13CD3Bu;
 PT_DEV float f_sqrt(float a) { return __builtin_sqrtf(a); } // correctly rounded (atmosphere precompute, uniform uses)
 // pt-f32 square root: two Newton steps y *= 1.5 - (x/2*y)*y on the classic inverse-square-root seed (4.7e-6), then one residual
 // correction s += (x - s*s) * y/2 (<= 0.501 ulp).  sqrt(0) = 0 exactly; negative, infinite and NaN inputs give a non-finite
