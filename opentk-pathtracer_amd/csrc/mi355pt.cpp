@@ -2193,6 +2193,16 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_build_sphere_grid
     return (int)g.packed.size();
 }
 
+// Test aid (not declared in the public header; needs no GPU): the run bits of the in-order sphere loop (FrameArgs::sphereRunStart) for a
+// std140 GameObjectsUBO with num_spheres spheres, exactly as ptgrid::sphere_runs hands them to the kernels: bit i of the 256 = sphere i
+// starts a new run.
+extern "C" __attribute__((visibility("default"))) int pt_debug_sphere_runs(const float *objects, int num_spheres, unsigned long long out[4])
+{
+    if (!objects || !out) return PT_E_BAD_ARGUMENT;
+    ptgrid::sphere_runs(objects, num_spheres, out);
+    return PT_OK;
+}
+
 // Test aid (not declared in the public header; needs no GPU): what launch_integrate would decide (pt::plan_launch) for a launch with
 // these arguments and these values of the kernel-selection knobs.  The process-wide knobs are not consulted and nothing is launched.
 // kernelRow: the row of the family's dispatch table the plan names (-1: none, or a family without a table).

@@ -269,6 +269,21 @@ def debug_set(key: str, value: int) -> None:
 
 
 
+def debug_sphere_runs(objects, num_spheres: int) -> int:
+    """The run bits of the in-order sphere loop (pt_debug_sphere_runs — exported, not in the public header; needs no GPU) for a
+    GameObjectsUBO blob (bytes or float32 array) as one 256-bit integer: bit i = sphere i starts a new run."""
+    import numpy as np
+    L = load()
+    L.pt_debug_sphere_runs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]
+    L.pt_debug_sphere_runs.restype = C.c_int
+    objs = np.frombuffer(objects, dtype=np.float32).copy() if isinstance(objects, (bytes, bytearray)) else np.ascontiguousarray(objects, dtype=np.float32)
+    if objs.size < 20 * min(max(int(num_spheres), 0), PT_MAX_SPHERES):
+        raise ValueError("objects shorter than num_spheres spheres")
+    out = (C.c_ulonglong * 4)()
+    check(L.pt_debug_sphere_runs(objs.ctypes.data, int(num_spheres), out))
+    return sum(int(out[w]) << (64 * w) for w in range(4))
+
+
 def debug_launch_stats(handle) -> dict:
     """How the handle has been launching (pt_debug_launch_stats — exported, not in the public header; neither flushes nor joins)."""
     L = load()
