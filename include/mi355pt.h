@@ -520,6 +520,44 @@ PT_API int pt_denoise_read_noise(pt_handle h, float *dst, size_t row_pitch_bytes
  * three cases of pt_denoise_read_noise. */
 PT_API int pt_denoise_noise_level(pt_handle h, float *out_mean_variance, int *out_observations, int *out_hit_pixels);
 
+/* ---- Adaptive sampling: per-tile sample counts driven by measured noise.  The reference spends every frame on every pixel
+ * (PathTracer.cs:114-129); these entry points stop where the image is done and keep sampling where it is not.  The image is divided into
+ * 8x8 tiles of the handle's own rows; every tile carries a record (k, k0, err, n): the samples its pixels hold, the count the statistics
+ * started at, the tile's noise estimate and its in-image pixel count.  One PASS gives every ACTIVE tile — k < max_samples and
+ * (k - k0 < min_samples - 1 or err > threshold), re-evaluated from the stored record at the start of every pass — one more frame with the
+ * tile's own frame index k.  A pixel's sample for frame index k depends on (x, y, k) and the inputs only, so a pixel that has received k
+ * samples holds bit for bit what k pt_render frames leave there.  err = the mean over the tile's pixels of e = M2 / ((k - k0) k) /
+ * (1 + l)^4, the variance of the pixel's mean carried to the tone-compressed luminance u = l / (1 + l) — pt_denoise_noise_level's unit —
+ * with M2 the Welford sum recovered from the running mean before and after each fold (the definition: DESIGN.md section 3.5).
+ * While an adaptive state is LIVE — from the pt_adaptive_render that initialises it until pt_reset, pt_write_result, pt_set_size,
+ * pt_set_tile, pt_set_interleaved_tile or pt_bind_result_buffer — pixels hold different sample counts: pt_get_frame_index keeps returning
+ * the frame index F the state started from, pt_render and a pt_denoise_render with the temporal stage or the moments on return
+ * PT_E_BAD_ARGUMENT and touch nothing; everything that only reads the image works unchanged.  A host that never calls
+ * pt_adaptive_render is not affected in any way.  Single-GPU handles, under pt_set_tile / pt_set_interleaved_tile too; a group handle:
+ * PT_E_BAD_ARGUMENT. */
+
+/* threshold: a variance of u, finite and >= 0 (else PT_E_BAD_ARGUMENT); min_samples 2..65535, max_samples min_samples..65535 (else
+ * PT_E_OUT_OF_RANGE); the previous values stay in force on an error.  Defaults 1e-4f (a standard deviation of 0.01, about 2.5 of the 255
+ * display levels before gamma), 8, 1024.  Read by the passes enqueued after the call. */
+PT_API int pt_adaptive_set_params(pt_handle h, float threshold, int min_samples, int max_samples);
+/* Enqueues `passes` passes (1..65535, else PT_E_OUT_OF_RANGE) on the stream in force: asynchronous, stream-ordered.  Pending pt_render
+ * frames are launched first.  Without a live state one is initialised from the frame index F: every tile k = F, k0 = max(F, 1),
+ * statistics zero — so a host may render its first frames with pt_render and go on adaptively, or start from frame 0.  The buffers (16
+ * bytes per tile, 8 per pixel) are allocated by the first call after a (re)size or (re)tiling.  PT_E_BAD_ARGUMENT under
+ * pt_set_arithmetic(PT_ARITH_REFERENCE); PT_E_NO_ENVIRONMENT without an environment. */
+PT_API int pt_adaptive_render(pt_handle h, int passes);
+/* Blocks.  *out_active_tiles = the tiles still active under the parameters in force, *out_tiles = the tile count, *out_pixel_samples =
+ * the sum over the pixels of their sample counts x spp, *out_min_count / *out_max_count = the smallest and largest k.  Any pointer may be
+ * NULL.  PT_E_BAD_ARGUMENT without a live state. */
+PT_API int pt_adaptive_status(pt_handle h, int *out_active_tiles, int *out_tiles, int64_t *out_pixel_samples, int *out_min_count,
+                              int *out_max_count);
+/* Blocks.  ceil(width / 8) x ceil(rows / 8) records of 16 bytes, row-major, tile row 0 = the handle's rows 0..7: (int32 k, int32 k0,
+ * float err, int32 n).  PT_E_BAD_ARGUMENT without a live state or for dst == NULL. */
+PT_API int pt_adaptive_read_tiles(pt_handle h, void *dst_16_bytes_per_tile);
+/* Blocks.  The per-pixel estimate e (the heat map a GUI would show), one float per pixel, rows like the image; row_pitch_bytes >=
+ * width*4, 0 = tightly packed.  PT_E_BAD_ARGUMENT without a live state, for dst == NULL or a pitch smaller than a row. */
+PT_API int pt_adaptive_read_noise(pt_handle h, float *dst, size_t row_pitch_bytes);
+
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);
 PT_API int pt_device_count(void);

@@ -360,6 +360,7 @@ int leave_tiling(pt_handle h)
     if (int rc = join_stripes(h)) return rc;
     if (int rc = ptimpl::free_first_hit(h)) return rc;
     if (int rc = ptimpl::free_denoise(h)) return rc;
+    if (int rc = ptimpl::free_adaptive(h)) return rc;
     h->resetEpoch++;
     return PT_OK;
 }
@@ -559,6 +560,8 @@ PT_API int pt_destroy(pt_handle h)
     if (h->dFirstHit) (void)hipFree(h->dFirstHit);
     if (h->dPick) (void)hipFree(h->dPick);
     (void)h->denoise.release();
+    if (h->adaptive.dTiles) (void)hipFree(h->adaptive.dTiles);
+    if (h->adaptive.dStats) (void)hipFree(h->adaptive.dStats);
     if (h->dTimeline) (void)hipFree(h->dTimeline);
     if (h->evBegin) (void)hipEventDestroy(h->evBegin);
     if (h->evEnd) (void)hipEventDestroy(h->evEnd);
@@ -1323,6 +1326,19 @@ bool gpu_busy(pt_handle h)
 
 namespace ptimpl {
 
+int plain_frame_args(pt_handle h, pt::FrameArgs &a, int frame)
+{
+    std::memset(&a, 0, sizeof a);
+    if (int rc = fill_frame_args(h, a, frame, 1)) return rc;
+    a.variant = 1;
+    a.y0 = h->y0;
+    a.rows = h->rows;
+    a.accum = h->accum();
+    a.tilesY = (h->rows + 7) / 8;
+    a.queue = h->dQueue;
+    return PT_OK;
+}
+
 int ensure_rgba8(pt_handle h)
 {
     size_t need = h->tilePixels();
@@ -1548,6 +1564,7 @@ PT_API int pt_render(pt_handle h, int *out_total_samples)
         if (out_total_samples) *out_total_samples = total;
         return PT_OK;
     }
+    if (h->adaptiveLive()) return fail(h, PT_E_BAD_ARGUMENT, "adaptive accumulation in progress: pt_reset first");
     if (!h->dEnv) return fail(h, PT_E_NO_ENVIRONMENT, "pt_render called before pt_set_environment / pt_atmosphere_render");
     if (h->boundAccum && h->boundBytes < h->tilePixels() * sizeof(float4))
         return fail(h, PT_E_BAD_ARGUMENT, "bound result buffer is smaller than the tile");
@@ -2040,6 +2057,7 @@ PT_API int pt_bind_result_buffer(pt_handle h, void *device_ptr, size_t bytes)
     if (int rc = ptimpl::fix_alpha(h)) return rc; // (the image rendered so far stays behind with alpha = 1)
     h->boundAccum = (float4 *)device_ptr;
     h->boundBytes = device_ptr ? bytes : 0;
+    h->adaptive.started = false; // (an adaptive state describes the image it was made on)
     // alpha doubles as the frame tag inside pipelined launches: whatever the caller's memory holds, it starts as 1
     if (device_ptr) PT_HIP(h, pt::launch_set_alpha(h->boundAccum, h->tilePixels(), h->stream));
     return audit_forget(h);

@@ -1,6 +1,8 @@
 // mi355pt_queries.cpp — the entry points of the C ABI (include/mi355pt.h) that ask something about the image without rendering it: the
-// first-hit query (pt_first_hit_*, pt_pick) and the preview denoiser (pt_denoise_*).  Both stand behind bind_device / join_stripes and
-// use nothing else of the launch pipeline of mi355pt.cpp; their buffers belong to a size and a tiling (free_first_hit, free_denoise).
+// first-hit query (pt_first_hit_*, pt_pick) and the preview denoiser (pt_denoise_*) — and, next to them, adaptive sampling (pt_adaptive_*),
+// which does render but only through a kernel of its own.  All stand behind bind_device / join_stripes and use nothing else of the launch
+// pipeline of mi355pt.cpp (adaptive sampling: its kernel argument, plain_frame_args); their buffers belong to a size and a tiling
+// (free_first_hit, free_denoise, free_adaptive).
 #include "pt_renderer.hpp"
 #include "pt_object_map.hpp"
 
@@ -37,6 +39,24 @@ int free_denoise(pt_handle h)
     if (!d.allocated()) return PT_OK;
     PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_denoise_render may still write them)
     PT_HIP(h, d.release());
+    return PT_OK;
+}
+
+int free_adaptive(pt_handle h)
+{
+    pt_renderer::Adaptive &ad = h->adaptive;
+    ad.started = false; // (the state belongs to a size and a tiling)
+    if (!ad.dTiles && !ad.dStats) return PT_OK;
+    PT_HIP(h, hipStreamSynchronize(h->stream)); // (a queued pt_adaptive_render may still write them)
+    hipError_t first = hipSuccess;
+    if (ad.dTiles) first = hipFree(ad.dTiles);
+    ad.dTiles = nullptr;
+    if (ad.dStats) {
+        const hipError_t e = hipFree(ad.dStats);
+        if (first == hipSuccess) first = e;
+    }
+    ad.dStats = nullptr;
+    PT_HIP(h, first);
     return PT_OK;
 }
 
@@ -453,6 +473,8 @@ PT_API int pt_denoise_render(pt_handle h, int guide_frame_index)
     PT_CHECK_HANDLE(h);
     if (guide_frame_index < 0) return fail(h, PT_E_BAD_ARGUMENT, "guide_frame_index must be >= 0");
     if (int rc = denoise_owner(h)) return rc;
+    if (h->adaptiveLive() && (h->denoise.temporal || h->denoise.moments))
+        return fail(h, PT_E_BAD_ARGUMENT, "adaptive accumulation in progress: the temporal stage and the moments rest on frame index x spp (pt_reset first)");
     return denoise_run(h, guide_frame_index, kDenoiseAll);
 }
 
@@ -635,6 +657,148 @@ PT_API int pt_denoise_present_rgba8(pt_handle h, uint8_t *dst, size_t row_pitch_
     if (int rc = ensure_rgba8(h)) return rc;
     PT_HIP(h, ptimpl::launch_tone_map(h->presentArithmetic, h->denoise.dImage[h->denoise.result], h->dRgba8, h->tilePixels(), h->stream));
     return denoise_copy_out(h, dst, row_pitch_bytes, h->dRgba8, 4);
+}
+
+// ---- adaptive sampling (pt_adaptive.hip): per-tile sample counts driven by a noise estimate the passes measure themselves.
+// The reference spends every frame on every pixel (PathTracer.cs:114-129); a pass spends one more sample on the tiles that still need it.
+// Writes the accumulation image, the tile records and the per-pixel statistics; the frame counter stays where pt_render left it.
+static int adaptive_owner(pt_handle h)
+{
+    if (h->isGroup()) return fail(h, PT_E_BAD_ARGUMENT, "adaptive sampling is not available on a group handle");
+    return PT_OK;
+}
+
+static int adaptive_live(pt_handle h)
+{
+    if (int rc = adaptive_owner(h)) return rc;
+    if (!h->adaptiveLive() || !h->adaptive.dTiles || !h->adaptive.dStats)
+        return fail(h, PT_E_BAD_ARGUMENT, "no adaptive state (no pt_adaptive_render since the last pt_reset / pt_write_result / pt_set_size / pt_set_tile / pt_set_interleaved_tile / pt_bind_result_buffer)");
+    return bind_device(h);
+}
+
+// the tile records as they stand once everything queued has run
+static int adaptive_fetch_tiles(pt_handle h, std::vector<int4> &rec)
+{
+    rec.resize((size_t)((h->width + 7) / 8) * (size_t)((h->rows + 7) / 8));
+    PT_HIP(h, hipMemcpyAsync(rec.data(), h->adaptive.dTiles, rec.size() * sizeof(int4), hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(h, hipStreamSynchronize(h->stream));
+    return PT_OK;
+}
+
+PT_API int pt_adaptive_set_params(pt_handle h, float threshold, int min_samples, int max_samples)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_owner(h)) return rc;
+    if (!std::isfinite(threshold) || !(threshold >= 0.0f)) return fail(h, PT_E_BAD_ARGUMENT, "threshold must be finite and >= 0");
+    if (min_samples < 2 || min_samples > 65535 || max_samples < min_samples || max_samples > 65535)
+        return fail(h, PT_E_OUT_OF_RANGE, "min_samples 2..65535, max_samples min_samples..65535");
+    h->adaptive.threshold = threshold; // (read by the passes enqueued from now on; what is queued already took its values)
+    h->adaptive.minSamples = min_samples;
+    h->adaptive.maxSamples = max_samples;
+    return PT_OK;
+}
+
+PT_API int pt_adaptive_render(pt_handle h, int passes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_owner(h)) return rc;
+    if (passes < 1 || passes > 65535) return fail(h, PT_E_OUT_OF_RANGE, "passes 1..65535");
+    if (h->arithmetic != PT_ARITH_CONTRACT) return fail(h, PT_E_BAD_ARGUMENT, "adaptive sampling renders in the contract arithmetic only (pt_set_arithmetic)");
+    if (!h->dEnv) return fail(h, PT_E_NO_ENVIRONMENT, "pt_adaptive_render called before pt_set_environment / pt_atmosphere_render");
+    if (h->boundAccum && h->boundBytes < h->tilePixels() * sizeof(float4))
+        return fail(h, PT_E_BAD_ARGUMENT, "bound result buffer is smaller than the tile");
+    if (int rc = bind_device(h)) return rc;
+    // (pending frames are launched, an open frame-fed launch is closed, an abandoned hand-over is repaired, alpha is back to 1)
+    if (int rc = ptimpl::fix_alpha(h)) return rc;
+    pt_renderer::Adaptive &ad = h->adaptive;
+    const int tilesX = (h->width + 7) / 8, tilesY = (h->rows + 7) / 8;
+    if (!ad.dTiles) PT_HIP(h, hipMalloc((void **)&ad.dTiles, (size_t)tilesX * tilesY * sizeof(int4)));
+    if (!ad.dStats) PT_HIP(h, hipMalloc((void **)&ad.dStats, h->tilePixels() * sizeof(float2)));
+    pt::FrameArgs a;
+    if (int rc = ptimpl::plain_frame_args(h, a, h->frame)) return rc;
+    if (!h->adaptiveLive()) {
+        PT_HIP(h, pt::launch_adaptive_init(ad.dTiles, tilesX, tilesY, h->width, h->rows, h->frame, h->stream));
+        PT_HIP(h, hipMemsetAsync(ad.dStats, 0, h->tilePixels() * sizeof(float2), h->stream));
+        ad.started = true;
+        ad.epoch = h->resetEpoch;
+    }
+    pt::AdaptiveArgs p;
+    p.tiles = ad.dTiles;
+    p.stats = ad.dStats;
+    p.threshold = ad.threshold;
+    p.minSamples = ad.minSamples;
+    p.maxSamples = ad.maxSamples;
+    for (int i = 0; i < passes; i++) PT_HIP(h, pt::launch_adaptive(a, p, h->stream));
+    return PT_OK;
+}
+
+PT_API int pt_adaptive_status(pt_handle h, int *out_active_tiles, int *out_tiles, int64_t *out_pixel_samples, int *out_min_count, int *out_max_count)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_live(h)) return rc;
+    std::vector<int4> rec;
+    if (int rc = adaptive_fetch_tiles(h, rec)) return rc;
+    const pt_renderer::Adaptive &ad = h->adaptive;
+    int active = 0, lo = rec[0].x, hi = rec[0].x;
+    long long samples = 0;
+    for (const int4 &r : rec) {
+        float err;
+        std::memcpy(&err, &r.z, sizeof err);
+        if (r.x < ad.maxSamples && (r.x - r.y < ad.minSamples - 1 || err > ad.threshold)) active++; // (the kernel's decision)
+        samples += (long long)r.x * r.w;
+        lo = r.x < lo ? r.x : lo;
+        hi = r.x > hi ? r.x : hi;
+    }
+    if (out_active_tiles) *out_active_tiles = active;
+    if (out_tiles) *out_tiles = (int)rec.size();
+    if (out_pixel_samples) *out_pixel_samples = (int64_t)(samples * h->spp);
+    if (out_min_count) *out_min_count = lo;
+    if (out_max_count) *out_max_count = hi;
+    return PT_OK;
+}
+
+PT_API int pt_adaptive_read_tiles(pt_handle h, void *dst_16_bytes_per_tile)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_live(h)) return rc;
+    if (!dst_16_bytes_per_tile) return fail(h, PT_E_BAD_ARGUMENT, "dst == NULL");
+    std::vector<int4> rec;
+    if (int rc = adaptive_fetch_tiles(h, rec)) return rc;
+    std::memcpy(dst_16_bytes_per_tile, rec.data(), rec.size() * sizeof(int4));
+    return PT_OK;
+}
+
+// word `word` of the per-pixel (M2, e) pairs, one float per pixel
+static int adaptive_copy_stat(pt_handle h, float *dst, size_t row_pitch_bytes, int word)
+{
+    if (!dst) return fail(h, PT_E_BAD_ARGUMENT, "dst == NULL");
+    const size_t rowBytes = (size_t)h->width * 4;
+    if (row_pitch_bytes == 0) row_pitch_bytes = rowBytes;
+    if (row_pitch_bytes < rowBytes) return fail(h, PT_E_BAD_ARGUMENT, "row pitch smaller than a row");
+    std::vector<float2> st(h->tilePixels());
+    PT_HIP(h, hipMemcpyAsync(st.data(), h->adaptive.dStats, st.size() * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(h, hipStreamSynchronize(h->stream));
+    for (int y = 0; y < h->rows; y++) {
+        float *row = (float *)((unsigned char *)dst + (size_t)y * row_pitch_bytes);
+        const float2 *src = st.data() + (size_t)y * h->width;
+        for (int x = 0; x < h->width; x++) row[x] = word ? src[x].y : src[x].x;
+    }
+    return PT_OK;
+}
+
+PT_API int pt_adaptive_read_noise(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_live(h)) return rc;
+    return adaptive_copy_stat(h, dst, row_pitch_bytes, 1);
+}
+
+// Test aid (not declared in the public header): the per-pixel M2 of the adaptive state, laid out like pt_adaptive_read_noise's map.
+extern "C" __attribute__((visibility("default"))) int pt_debug_adaptive_read_m2(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_live(h)) return rc;
+    return adaptive_copy_stat(h, dst, row_pitch_bytes, 0);
 }
 
 // Timing aid (not declared in the public header): one stage of pt_denoise_render on its own — stage -1 = the guide kernel, i >= 0 = pass i

@@ -1,5 +1,5 @@
-// pt_kernels.hpp — host-visible launch interface of the HIP kernels (implemented in pt_integrate_persistent.hip, pt_integrate_multisample.hip
-// and pt_helper_kernels.hip).
+// pt_kernels.hpp — host-visible launch interface of the HIP kernels (implemented in pt_integrate_persistent.hip, pt_integrate_multisample.hip,
+// pt_helper_kernels.hip and the files named at the declarations).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -314,6 +314,18 @@ hipError_t launch_moments_blend(const MomentsBlendArgs &a, hipStream_t stream);
 // pt_denoise_noise_level: partial[i] = (binary32 sum of noise over the pixels with id >= 0 among pixels 256 i .. 256 i + 255, their count
 // as int bits); partial holds (pixels + 255) / 256 entries
 hipError_t launch_moments_level(const float *noise, const float4 *guides, float2 *partial, size_t pixels, hipStream_t stream);
+// adaptive sampling (pt_adaptive_render; pt_adaptive.hip).  One pass over the launch described by `a` (a plain launch over
+// the handle's rows, a.tilesX / a.tilesY set; a.frame is not read): every tile whose record says it is active under the parameters gets
+// one more sample per pixel with its own frame index; tiles = tilesX x tilesY records (k, k0, err bits, n), stats = (M2, e) per pixel
+struct AdaptiveArgs {
+    int4 *tiles;
+    float2 *stats;
+    float threshold;
+    int minSamples, maxSamples;
+};
+hipError_t launch_adaptive(const FrameArgs &a, const AdaptiveArgs &ad, hipStream_t stream);
+// the records of a fresh state: (frame, max(frame, 1), +0, in-image pixels of the tile)
+hipError_t launch_adaptive_init(int4 *tiles, int tilesX, int tilesY, int width, int rows, int frame, hipStream_t stream);
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 // the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);

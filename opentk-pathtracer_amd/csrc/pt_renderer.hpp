@@ -262,6 +262,19 @@ struct pt_renderer {
     } denoise;
     // bumped by pt_reset, pt_write_result, pt_set_size, pt_set_tile, pt_set_interleaved_tile: a denoiser set of an earlier epoch is history
     unsigned long long resetEpoch = 0;
+    // Adaptive sampling (pt_adaptive_render, pt_adaptive.hip): dTiles = one record (k, k0, err, n) of 16 bytes per 8x8 tile
+    // of the handle's rows, dStats = (M2, e) per pixel; both allocated by the first pt_adaptive_render after a (re)size or (re)tiling and
+    // freed by the next one — never on the pt_render path.  The state is LIVE from the pt_adaptive_render that initialises it until the
+    // reset epoch changes or pt_bind_result_buffer is called: pixels then hold different sample counts, `frame` stays what it was.
+    struct Adaptive {
+        int4 *dTiles = nullptr;
+        float2 *dStats = nullptr;
+        float threshold = 1e-4f; // pt_adaptive_set_params
+        int minSamples = 8, maxSamples = 1024;
+        bool started = false;    // a state was initialised ...
+        unsigned long long epoch = 0; // ... in this reset epoch
+    } adaptive;
+    bool adaptiveLive() const { return adaptive.started && adaptive.epoch == resetEpoch; }
 
     // hand-over audit (only allocated by the -DPT_AUDIT build, see pt_debug_hooks.hpp): side word per accumulation pixel + violation log
     unsigned long long *dAudit = nullptr;
@@ -426,6 +439,10 @@ int group_result_device_ptr(pt_handle g, void **out_ptr, size_t *out_bytes);
 int group_timer_end(pt_handle g, float *out_ms);
 int free_first_hit(pt_handle h); // the first-hit records belong to a size and a tiling: whoever changes either drops them (streams joined)
 int free_denoise(pt_handle h);   // ... and so do the denoiser's guides and images
+int free_adaptive(pt_handle h);  // ... and the adaptive state's tile records and statistics
+// the kernel argument of ONE plain launch over the handle's rows with the inputs in force (what variant 1 is launched with; the sphere
+// grid of a changed scene is rebuilt as for any launch), for pt_adaptive_render.  Call behind join_stripes
+int plain_frame_args(pt_handle h, pt::FrameArgs &a, int frame);
 int group_first_hit_read(pt_handle g, void *dst, size_t row_pitch_bytes);
 int group_pick(pt_handle g, int x, int y, int frame_index, int *out_id, float *out_t, float *out_origin, float *out_dir);
 

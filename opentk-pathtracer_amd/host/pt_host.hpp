@@ -428,6 +428,33 @@ public:
         Check(pt_denoise_noise_level(h_, &mean, observations, hitPixels), h_);
         return mean;
     }
+    // Adaptive sampling: per-tile sample counts driven by measured noise.  A tile stays active while it holds fewer than maxSamples samples
+    // and either fewer than minSamples since its statistics started or a noise estimate above threshold
+    void SetAdaptive(float threshold = 1e-4f, int minSamples = 8, int maxSamples = 1024) { Check(pt_adaptive_set_params(h_, threshold, minSamples, maxSamples), h_); }
+    // `passes` passes, each one more sample per pixel of every tile still active (asynchronous); until ResetRenderer(), Render() fails
+    void RenderAdaptive(int passes = 1) { Check(pt_adaptive_render(h_, passes), h_); }
+    struct AdaptiveState { int activeTiles, tiles; int64_t pixelSamples; int minCount, maxCount; };
+    AdaptiveState AdaptiveStatus() const
+    {
+        AdaptiveState s{};
+        Check(pt_adaptive_status(h_, &s.activeTiles, &s.tiles, &s.pixelSamples, &s.minCount, &s.maxCount), h_);
+        return s;
+    }
+    struct AdaptiveTile { int32_t k, k0; float err; int32_t n; };
+    // the tile records, row-major, ceil(width / 8) per tile row
+    std::vector<AdaptiveTile> AdaptiveTiles() const
+    {
+        std::vector<AdaptiveTile> tiles((size_t)((width_ + 7) / 8) * (size_t)((height_ + 7) / 8));
+        Check(pt_adaptive_read_tiles(h_, tiles.data()), h_);
+        return tiles;
+    }
+    // the per-pixel noise estimate: one float per pixel, row 0 = bottom
+    std::vector<float> AdaptiveNoise() const
+    {
+        std::vector<float> noise((size_t)width_ * height_);
+        Check(pt_adaptive_read_noise(h_, noise.data(), 0), h_);
+        return noise;
+    }
     // ScreenEffect.Render (src/Render/ScreenEffect.cs:29-37) of the last Denoise() instead of `Result`
     std::vector<uint8_t> PresentDenoised() const
     {

@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("MI355PT_LIB") or os.path.join(HERE, "libmi355pt.so")  # MI355PT_LIB: A/B tuning builds
 HEADER = os.path.join(REPO, "include", "mi355pt.h")
 SOURCES = ["pt_integrate_persistent.hip", "pt_integrate_multisample.hip", "pt_integrate_reference.hip", "pt_first_hit.hip", "pt_denoise.hip",
-           "pt_denoise_moments.hip", "pt_helper_kernels.hip", "mi355pt.cpp", "mi355pt_queries.cpp", "mi355pt_multi.cpp"]
+           "pt_denoise_moments.hip", "pt_adaptive.hip", "pt_helper_kernels.hip", "mi355pt.cpp", "mi355pt_queries.cpp", "mi355pt_multi.cpp"]
 # -ffp-contract=off / -fno-fast-math are part of the pt-f32 arithmetic contract (csrc/pt_math.hpp)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-shared",
                "-fvisibility=hidden"]
@@ -237,6 +237,11 @@ def load() -> C.CDLL:
         "pt_denoise_set_moments": [vp, C.c_int, C.c_int],
         "pt_denoise_read_noise": [vp, fp, C.c_size_t],
         "pt_denoise_noise_level": [vp, fp, ip, ip],
+        "pt_adaptive_set_params": [vp, C.c_float, C.c_int, C.c_int],
+        "pt_adaptive_render": [vp, C.c_int],
+        "pt_adaptive_status": [vp, ip, ip, C.POINTER(C.c_int64), ip, ip],
+        "pt_adaptive_read_tiles": [vp, vp],
+        "pt_adaptive_read_noise": [vp, fp, C.c_size_t],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -317,6 +322,17 @@ def debug_denoise_stage(handle, frame: int, stage: int) -> None:
     L.pt_debug_denoise_stage.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pt_debug_denoise_stage.restype = C.c_int
     check(L.pt_debug_denoise_stage(handle, frame, stage), handle)
+
+
+def debug_adaptive_m2(handle, rows: int, width: int):
+    """The per-pixel M2 of the adaptive state (pt_debug_adaptive_read_m2 — exported, not in the public header) as (rows, width) float32."""
+    import numpy as np
+    L = load()
+    L.pt_debug_adaptive_read_m2.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
+    L.pt_debug_adaptive_read_m2.restype = C.c_int
+    out = np.empty((rows, width), dtype=np.float32)
+    check(L.pt_debug_adaptive_read_m2(handle, out.ctypes.data_as(C.POINTER(C.c_float)), 0), handle)
+    return out
 
 
 def debug_denoise_var0(handle, rows: int, width: int):

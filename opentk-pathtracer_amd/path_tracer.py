@@ -27,6 +27,9 @@ assert GUIDE_DTYPE.itemsize == 32
 # an entry of the object map (pt_denoise_read_object_map): history point = a * P + b per component, state = PT_TRACK_KEEP / MOVED / DROP
 OBJECT_MAP_DTYPE = np.dtype([("a", np.float32, 3), ("state", np.int32), ("b", np.float32, 3), ("zero", np.int32)])
 assert OBJECT_MAP_DTYPE.itemsize == 32
+# a tile record of pt_adaptive_read_tiles: samples held, the count the statistics started at, the tile's noise estimate, in-image pixels
+ADAPTIVE_TILE_DTYPE = np.dtype([("k", np.int32), ("k0", np.int32), ("err", np.float32), ("n", np.int32)])
+assert ADAPTIVE_TILE_DTYPE.itemsize == 16
 
 
 class EnvironmentMap:
@@ -401,6 +404,35 @@ class PathTracer:
         mean, k, hit = C.c_float(), C.c_int(), C.c_int()
         check(self._lib.pt_denoise_noise_level(self._h, C.byref(mean), C.byref(k), C.byref(hit)), self._h)
         return float(mean.value), int(k.value), int(hit.value)
+
+    # -- adaptive sampling (per-tile sample counts driven by measured noise)
+    def SetAdaptive(self, threshold: float = 1e-4, min_samples: int = 8, max_samples: int = 1024) -> None:
+        """pt_adaptive_set_params: a tile stays active while it holds fewer than max_samples samples and either fewer than min_samples
+        since its statistics started or a noise estimate (variance of the tone-compressed luminance) above threshold."""
+        check(self._lib.pt_adaptive_set_params(self._h, threshold, min_samples, max_samples), self._h)
+
+    def RenderAdaptive(self, passes: int = 1) -> None:
+        """pt_adaptive_render: `passes` passes, each one more sample per pixel of every tile still active.  Asynchronous.  The first call
+        starts an adaptive state from the frames rendered so far; until ResetRenderer, Render raises and FrameIndex stays."""
+        check(self._lib.pt_adaptive_render(self._h, passes), self._h)
+
+    def AdaptiveStatus(self) -> dict:
+        """pt_adaptive_status: -> active_tiles, tiles, pixel_samples (sum over pixels of sample count x spp), min_count, max_count."""
+        a, t, lo, hi, s = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        check(self._lib.pt_adaptive_status(self._h, C.byref(a), C.byref(t), C.byref(s), C.byref(lo), C.byref(hi)), self._h)
+        return {"active_tiles": a.value, "tiles": t.value, "pixel_samples": s.value, "min_count": lo.value, "max_count": hi.value}
+
+    def AdaptiveTiles(self) -> np.ndarray:
+        """pt_adaptive_read_tiles: the tile records as a (ceil(rows / 8), ceil(Width / 8)) structured array (ADAPTIVE_TILE_DTYPE)."""
+        out = np.empty(((self.rows + 7) // 8, (self.Width + 7) // 8), dtype=ADAPTIVE_TILE_DTYPE)
+        check(self._lib.pt_adaptive_read_tiles(self._h, out.ctypes.data_as(C.c_void_p)), self._h)
+        return out
+
+    def AdaptiveNoise(self) -> np.ndarray:
+        """pt_adaptive_read_noise: the per-pixel noise estimate e as (rows, Width) float32."""
+        out = np.empty((self.rows, self.Width), dtype=np.float32)
+        check(self._lib.pt_adaptive_read_noise(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
+        return out
 
     def PresentDenoised(self) -> np.ndarray:
         """pt_denoise_present_rgba8: the result of the last Denoise through the tone map Present applies, as (rows, Width, 4) uint8."""
