@@ -176,3 +176,98 @@ def test_grid_walk_cost_model_runs_and_orders_the_control_structures():
     ideal, lock, flat, cont = num("ideal (all lanes busy)"), num("lock-step rounds (today)"), num("flattened per-lane state machine"), num("continuous refill (no phase end)")
     pool64 = num("refill from a pool of 64 + 64 rays")
     assert ideal < cont < pool64 < lock < flat, p.stdout
+
+
+# ---------------------------------------------------------------------------------------------- the grids of the degenerate-scene table
+def build_blob(native_lib, blob, ns):
+    """build() for a GameObjectsUBO blob (tests/degenerate_cases.py patches blobs: Material and Sphere clamp or convert)"""
+    fn = native_lib.pt_debug_build_sphere_grid
+    fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_void_p, C.c_int]
+    objs = np.frombuffer(blob, dtype=np.float32).copy()
+    header, box = (C.c_int * 5)(), (C.c_float * 10)()
+    packed = np.zeros(4096, np.uint8)
+    n = fn(objs.ctypes.data, ns, header, box, packed.ctypes.data, packed.nbytes)
+    dims = np.array(header[0:3])
+    cells = int(dims.prod())
+    starts = packed[:2 * (cells + 1)].view(np.uint16).astype(int)
+    refs = packed[2 * (cells + 1):2 * (cells + 1) + header[3]].astype(int)
+    return dict(valid=bool(header[4]), dims=dims, nrefs=header[3], lo=np.array(box[0:3], np.float64), hi=np.array(box[3:6], np.float64),
+                center=np.array(box[6:9], np.float64), reach2=float(box[9]), starts=starts, refs=refs, nbytes=n)
+
+
+def resume_margin(g):
+    """How many times the smallest cell extent exceeds the error of the point at which a walk cut short is resumed (ray_trace_t<GRID>,
+    csrc/pt_device.hpp: p = fma(d, walkFrom, o), walkFrom = the exit parameter of the last cell processed).  The exit parameter is
+    (plane - o) * rcp(d): two roundings and a reciprocal good to 1 ulp, at most 4 * 2^-23 relative, of a length of at most
+    D = reach + the box's diagonal; the fused multiply-add adds half an ulp of a coordinate of at most M + D."""
+    ext = g["hi"] - g["lo"]
+    D = np.sqrt(g["reach2"]) + np.linalg.norm(ext)
+    M = max(np.abs(g["lo"]).max(), np.abs(g["hi"]).max())
+    delta = 4 * 2.0 ** -23 * D + 2.0 ** -24 * (M + D)
+    return float((ext / g["dims"]).min() / delta)
+
+
+def assert_structure(g, ns):
+    cells = int(g["dims"].prod())
+    assert g["valid"] and cells <= 256 and g["nrefs"] <= 1024 and g["nbytes"] % 4 == 0 and (g["dims"] >= 1).all() and (g["dims"] <= 32).all()
+    assert g["starts"][0] == 0 and g["starts"][cells] == g["nrefs"] and (np.diff(g["starts"]) >= 0).all()
+    for c in range(cells):
+        assert (np.diff(g["refs"][g["starts"][c]:g["starts"][c + 1]]) > 0).all()
+    assert set(g["refs"]) == set(range(ns)), "every sphere, zero radii included, is listed somewhere"
+    assert (g["hi"] > g["lo"]).all() and g["reach2"] > 0
+
+
+def test_grids_of_the_degenerate_scene_table(native_lib):
+    """What ptgrid::build returns for the F6 and tier-N blobs of tests/degenerate_cases.py with at least 64 spheres — each case records it
+    (Case.grid) — and, for every grid it does return, the two facts the termination argument of tests/test_gpu_degenerate.py rests on: every
+    cell is many times wider than the error of a resumed walk's entry point, and no axis has more than 32 cells."""
+    import degenerate_cases as dc
+    seen = set()
+    for case in dc.CASES:
+        b = dc.built(case)
+        if case.grid is None:
+            assert b.ns < 64
+            continue
+        g = build_blob(native_lib, b.blob, b.ns)
+        assert g["valid"] == case.grid, case.name
+        seen.add(case.grid)
+        if g["valid"]:
+            assert_structure(g, b.ns)
+            m = resume_margin(g)
+            print(f"{case.name}: {b.ns} spheres, grid {g['dims'].tolist()}, {g['nrefs']} references, smallest cell = {m:.0f} x the resume error")
+            assert m >= 16
+    assert seen == {True, False}
+    # zero radii among 64 (f6_f1_64), every centre in one plane (f6_plane_64), a radius of 1e19 (f6_huge_64: `Rg < 1e15`), NaN among 64
+    assert dc.BY_NAME["f6_f1_64"].grid and dc.BY_NAME["f6_plane_64"].grid and not dc.BY_NAME["f6_huge_64"].grid and not dc.BY_NAME["n_grid_refused"].grid
+    flat = build_blob(native_lib, dc.built(dc.BY_NAME["f6_plane_64"]).blob, 64)
+    assert flat["dims"][2] == 1  # (centres in the plane z = -12: one layer of cells)
+
+
+@pytest.mark.parametrize("radius", [0.0, -0.0, 1e-40, 1e-20])
+def test_grid_of_zero_radius_spheres_in_one_plane(native_lib, radius):
+    """The extreme of those grids: 64 spheres of radius zero (or a denormal, or 1e-20) with every centre in one plane.  The box is as
+    thin as it gets — the sqrt(2 err) margin and the walk slack on either side of the plane — and a cell is still far wider than the
+    resume error; a single line of centres and a single point likewise, or the grid is refused."""
+    import degenerate_cases as dc
+    for layout in ("plane", "line", "point"):
+        blob = bytearray(26624)
+        for i in range(64):
+            x, y = (i % 8, i // 8) if layout == "plane" else ((i, 0) if layout == "line" else (0, 0))
+            dc.patch_sphere(blob, i, centre=(-9.0 + 2.5 * x, -4.0 + 1.25 * y, -12.0), radius=radius)
+        g = build_blob(native_lib, bytes(blob), 64)
+        if layout == "point":
+            assert not g["valid"]  # (no extent: `Rg > 0` refuses it)
+            continue
+        assert_structure(g, 64)
+        thin = (g["hi"] - g["lo"]).min()
+        m = resume_margin(g)
+        print(f"radius {radius}, {layout}: grid {g['dims'].tolist()}, thinnest extent {thin:.3g}, smallest cell = {m:.0f} x the resume error")
+        assert m >= 16
+
+
+def test_grid_is_refused_for_huge_radii(native_lib):
+    import degenerate_cases as dc
+    for radius in (1e15, 1e19, -1e19, 1e20, 3e38):
+        blob = bytearray(dc.built(dc.BY_NAME["f6_f1_64"]).blob)
+        dc.patch_sphere(blob, 4, radius=radius)
+        assert not build_blob(native_lib, bytes(blob), 64)["valid"], radius

@@ -1,6 +1,7 @@
 """The host's object map (csrc/pt_object_map.hpp, what pt_denoise_render builds for pt_denoise_set_object_tracking) without a GPU: the
 header compiled on its own with g++ and compared, byte for byte, with the numpy restatement (tests/denoise_tracking_reference.py) on
-the classification table of tests/test_denoise_tracking_cpu.py — degenerate geometry, which no GPU test renders, included."""
+the classification table of tests/test_denoise_tracking_cpu.py — degenerate geometry, which no GPU test of the denoiser renders, included
+(the integrator's own degenerate scenes: tests/degenerate_cases.py)."""
 import ctypes as C
 import os
 import struct
