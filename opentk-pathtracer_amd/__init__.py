@@ -5,7 +5,7 @@ The directory name contains a hyphen (repo contract), so import it through __gra
 which registers it as the module `opentk_pathtracer_amd`.
 
   csrc/            hand-written HIP kernels (pt_integrate_persistent.hip, pt_integrate_multisample.hip, pt_helper_kernels.hip + device functions pt_device.hpp / pt_atmosphere.hpp), device math
-                   contract (pt_math.hpp), C ABI (mi355pt.cpp)
+                   contract (pt_math.hpp), C ABI (mi355pt.cpp + mi355pt_launch / _handover / _present / _debug / _queries / _multi.cpp)
   native.py        hipcc build recipe + ctypes binding of libmi355pt.so (fails loudly; no CPU fallback)
   path_tracer.py   host-side mirror of the reference's PathTracer / AtmosphericScatterer classes over the C ABI
   scene.py         Material / Sphere / Cuboid std140 packers + the reference's default scene data

@@ -1,7 +1,7 @@
 // mi355pt_queries.cpp — the entry points of the C ABI (include/mi355pt.h) that ask something about the image without rendering it: the
 // first-hit query (pt_first_hit_*, pt_pick) and the preview denoiser (pt_denoise_*) — and, next to them, adaptive sampling (pt_adaptive_*),
 // which does render but only through a kernel of its own.  All stand behind bind_device / join_stripes and use nothing else of the launch
-// pipeline of mi355pt.cpp (adaptive sampling: its kernel argument, plain_frame_args); their buffers belong to a size and a tiling
+// pipeline of mi355pt_launch.cpp (adaptive sampling: its kernel argument, plain_frame_args); their buffers belong to a size and a tiling
 // (free_first_hit, free_denoise, free_adaptive).
 #include "pt_renderer.hpp"
 #include "pt_object_map.hpp"
@@ -94,8 +94,8 @@ static void first_hit_args(pt_handle h, pt::FrameArgs &a, int frame_index)
     a.batchFrames = 1;
     a.frame = frame_index;
     a.objects = h->dObjects;
-    a.tilesX = (h->width + 7) / 8;
-    a.tilesY = (h->rows + 7) / 8;
+    a.tilesX = h->tilesX();
+    a.tilesY = h->tilesY();
 }
 
 PT_API int pt_first_hit_set_ray(pt_handle h, int mode)
@@ -679,7 +679,7 @@ static int adaptive_live(pt_handle h)
 // the tile records as they stand once everything queued has run
 static int adaptive_fetch_tiles(pt_handle h, std::vector<int4> &rec)
 {
-    rec.resize((size_t)((h->width + 7) / 8) * (size_t)((h->rows + 7) / 8));
+    rec.resize((size_t)h->tilesPerFrame());
     PT_HIP(h, hipMemcpyAsync(rec.data(), h->adaptive.dTiles, rec.size() * sizeof(int4), hipMemcpyDeviceToHost, h->stream));
     PT_HIP(h, hipStreamSynchronize(h->stream));
     return PT_OK;
@@ -711,7 +711,7 @@ PT_API int pt_adaptive_render(pt_handle h, int passes)
     // (pending frames are launched, an open frame-fed launch is closed, an abandoned hand-over is repaired, alpha is back to 1)
     if (int rc = ptimpl::fix_alpha(h)) return rc;
     pt_renderer::Adaptive &ad = h->adaptive;
-    const int tilesX = (h->width + 7) / 8, tilesY = (h->rows + 7) / 8;
+    const int tilesX = h->tilesX(), tilesY = h->tilesY();
     if (!ad.dTiles) PT_HIP(h, hipMalloc((void **)&ad.dTiles, (size_t)tilesX * tilesY * sizeof(int4)));
     if (!ad.dStats) PT_HIP(h, hipMalloc((void **)&ad.dStats, h->tilePixels() * sizeof(float2)));
     pt::FrameArgs a;

@@ -51,7 +51,7 @@ struct FrameArgs {
     int materialsInLds;     // set by the launch: 1 = the 64-byte materials are staged in LDS, 0 = read from `objects` (large scenes)
     unsigned long long *timeline; // optional (tuning): per wavefront {start, queue exhausted, end, iterations} timestamps
     // Launch chaining: every workgroup of a tagged launch stores launchSeq into startedFlags[blockIdx.x] (host-visible memory)
-    // when it starts, so that the host can tell whether the launch is fully RESIDENT (see launch_frames in mi355pt.cpp)
+    // when it starts, so that the host can tell whether the launch is fully RESIDENT (see launch_frames in mi355pt_launch.cpp)
     unsigned int *startedFlags;
     unsigned int launchSeq; // sequence number of this launch on its handle (every tagged launch has one; never 0)
     // Hand-over bound (round 5).  A result whose pixel does not show the previous frame's tag within waitBudget (wall clock, units of
@@ -86,7 +86,7 @@ struct FrameArgs {
     // spheres that ANY primary ray of the tile can reach, whatever the jitter and the lens sample — computed once per camera / scene by
     // pt_tile_masks_kernel (tile_cone in pt_device.hpp) and read with scalar loads by every frame's tile pass
     const unsigned long long *tileMasks; // kTileMaskWords words per tile: [0..3] spheres, [4] cuboids
-    // Present snapshot (non-blocking present, mi355pt.cpp pt_present_rgba8_async): when set, the resolve of the launch's LAST frame
+    // Present snapshot (non-blocking present, mi355pt_present.cpp pt_present_rgba8_async): when set, the resolve of the launch's LAST frame
     // also stores the pixel's new value here (same indexing as accum) — a consistent image of that frame that later frames never
     // touch, so the tone map can read it while the next launch (chained, ordered per pixel by the tags) already overwrites accum.
     float4 *snapshot;
@@ -131,7 +131,7 @@ struct FrameArgs {
 // Two frames that can be in the image together must have different tags, and the repair pass tells "a later launch's tag" from "an
 // older one" by the half window: every frame the host can have issued since the oldest launch it still remembers must lie within
 // kFrameTagMask / 2 of it.  The host remembers at most kMaxUnverifiedLaunches launches of at most kMaxBatchFrames frames (the bound is
-// enforced where launches are remembered, mi355pt.cpp): 128 x 256 = 32,768 frames, a sixteenth of the half window of 524,288.
+// enforced where launches are remembered, mi355pt_handover.cpp): 128 x 256 = 32,768 frames, a sixteenth of the half window of 524,288.
 // (Rounds 2 - 5 used a 1,024-frame window, which 256-frame launches of a small share could outrun: round-5 advisor finding.)
 constexpr int kFrameTagMask = 0xFFFFF;
 constexpr int kMaxBatchFrames = 256, kMaxUnverifiedLaunches = 128;

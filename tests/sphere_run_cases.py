@@ -173,7 +173,7 @@ GRID_OFF = dict(noSphereGrid=1, hasGrid=1, gridBytes=1024)  # a scene the host h
 
 def launch_forms(width: int, height: int, spp: int, frames: int):
     """The ways frames of a default-variant handle reach the GPU (choose_launch_mode, launch_striped, launch_single_stream in
-    csrc/mi355pt.cpp), as plan inputs without the scene: -> {name: dict}.
+    csrc/mi355pt_launch.cpp), as plan inputs without the scene: -> {name: dict}.
       striped    one frame on an idle handle that has not pipelined yet: untagged; two row stripes, each a launch of its own without drain
                  compaction — or, with fewer than 32 rows, ONE launch with drain compaction (32)
       pipelined  `frames` consecutive frames in one tagged launch over the whole image (also single frames, when the GPU is still busy

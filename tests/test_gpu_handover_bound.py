@@ -1,4 +1,4 @@
-"""GPU tests of the hand-over bound (round 5; csrc/pt_kernel_common.hpp "hand-over bound", csrc/mi355pt.cpp join_stripes).
+"""GPU tests of the hand-over bound (round 5; csrc/pt_kernel_common.hpp "hand-over bound", csrc/mi355pt_handover.cpp join_stripes).
 
 A pipelined launch orders the frames of a pixel through alpha tags; a result that has to wait for its pixel's previous frame waits at
 most FrameArgs::waitBudget of WALL CLOCK.  When that runs out the result is never folded onto a stale pixel (rounds 2-4 did that and

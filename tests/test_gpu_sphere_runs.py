@@ -31,7 +31,7 @@ def want(oracle, blob, sc_or_kw, frames, width=R.WIDTH, height=R.HEIGHT, spp=1, 
 
 def pipeline_first(pkg, pt):
     """Make the handle one that has pipelined frames, then restart it: from then on it launches single frames tagged too, as ONE launch over
-    the whole image (choose_launch_mode, csrc/mi355pt.cpp), instead of two untagged row stripes — the launch forms `pipelined1` /
+    the whole image (choose_launch_mode, csrc/mi355pt_launch.cpp), instead of two untagged row stripes — the launch forms `pipelined1` /
     `pipelinedN` of sphere_run_cases.launch_forms, whose rows test_sphere_runs_cpu.py pins."""
     for _ in range(16):  # (frames are held back while the GPU is busy with the handle's earlier ones: the first eight do it in practice)
         for _ in range(8):
