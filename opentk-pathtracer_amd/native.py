@@ -108,6 +108,31 @@ def build_variant(name: str, force: bool = False) -> str:
     return out
 
 
+# Device probe (tools/pt_device_probe.hip; tests/test_gpu_math_probe.py): the primitives of csrc/pt_math.hpp and the leaf functions of
+# csrc/pt_device.hpp one call per lane, built with the product's own flags.  A test aid outside csrc/: csrc_hash(), needs_build() and
+# the product library do not know it.
+#   probe      HIPCC_FLAGS as they are
+#   probe_ftz  + -fgpu-flush-denormals-to-zero: the CONTROL, a build that breaks the contract (the tests must see it differ)
+PROBES = {"probe": [], "probe_ftz": ["-fgpu-flush-denormals-to-zero"]}
+PROBE_SRC = os.path.join(REPO, "tools", "pt_device_probe.hip")
+
+
+def probe_path(name: str) -> str:
+    return os.path.join(HERE, f"libmi355pt_{name}.so")
+
+
+def build_probe(name: str, force: bool = False) -> str:
+    out = probe_path(name)
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [PROBE_SRC]
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
+        return out
+    cmd = [hipcc_path()] + HIPCC_FLAGS + PROBES[name] + ["-I", CSRC, PROBE_SRC, "-o", out]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode != 0:
+        raise RuntimeError(f"hipcc failed building {out}:\n" + p.stdout + p.stderr)
+    return out
+
+
 def build_stress_tool(force: bool = False) -> str:
     """g++ tools/handover_stress.cpp (dlopens whichever build of the library it is pointed at)."""
     src = os.path.join(REPO, "tools", "handover_stress.cpp")

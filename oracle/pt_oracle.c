@@ -966,6 +966,35 @@ PTO_API float pto_log(float x) { return f_log(x); }
 PTO_API void pto_rcp_array(const float *x, float *y, int n) { for (int i = 0; i < n; i++) y[i] = f_rcp(x[i]); }
 PTO_API void pto_rsqrt_array(const float *x, float *y, int n) { for (int i = 0; i < n; i++) y[i] = f_rsqrt(x[i]); }
 PTO_API void pto_sqrt_array(const float *x, float *y, int n) { for (int i = 0; i < n; i++) y[i] = pt_sqrt(x[i]); }
+/* array forms of the other primitives and leaf functions (tests/test_math_probe_cpu.py, tests/test_gpu_math_probe.py): every row goes
+ * through memory as it is, so a signalling NaN reaches the function unquieted, which an argument passed as a double would not */
+PTO_API void pto_mix_array(const float *x, const float *y, const float *a, float *out, int n) { for (int i = 0; i < n; i++) out[i] = f_mix(x[i], y[i], a[i]); }
+PTO_API void pto_sincos_array(const float *a, float *s, float *c, int n) { for (int i = 0; i < n; i++) f_sincos(a[i], s + i, c + i); }
+PTO_API void pto_exp_array(const float *x, float *y, int n) { for (int i = 0; i < n; i++) y[i] = f_exp(x[i]); }
+PTO_API void pto_log_array(const float *x, float *y, int n) { for (int i = 0; i < n; i++) y[i] = f_log(x[i]); }
+PTO_API void pto_pow5_array(const float *x, float *y, int n) { for (int i = 0; i < n; i++) y[i] = f_pow5(x[i]); }
+PTO_API void pto_aces_film_array(const float *x, float *y, int n) { for (int i = 0; i < n; i++) y[i] = aces_film(x[i]); }
+PTO_API void pto_linear_to_inverse_gamma_array(const float *v, float gamma, float *y, int n) { for (int i = 0; i < n; i++) y[i] = linear_to_inverse_gamma(v[i], gamma); }
+PTO_API void pto_to_unorm8_array(const float *v, uint8_t *y, int n) { for (int i = 0; i < n; i++) y[i] = to_unorm8(v[i]); }
+PTO_API void pto_pcg_hash_array(const uint32_t *seed, uint32_t *word, uint32_t *seed_out, int n)
+{ for (int i = 0; i < n; i++) { uint32_t s = seed[i]; word[i] = pcg_hash(&s); seed_out[i] = s; } }
+PTO_API void pto_rand01_array(const uint32_t *seed, float *value, uint32_t *seed_out, int n)
+{ for (int i = 0; i < n; i++) { uint32_t s = seed[i]; value[i] = rand01(&s); seed_out[i] = s; } }
+PTO_API void pto_pixel_seed_array(const int *xyf, uint32_t *seed, int n) { for (int i = 0; i < n; i++) seed[i] = pto_pixel_seed(xyf[3 * i], xyf[3 * i + 1], xyf[3 * i + 2]); }
+#define ROW3(p_, i_) V((p_)[3 * (i_)], (p_)[3 * (i_) + 1], (p_)[3 * (i_) + 2])
+#define PUT3(p_, i_, v_) do { v3 r_ = (v_); (p_)[3 * (i_)] = r_.x; (p_)[3 * (i_) + 1] = r_.y; (p_)[3 * (i_) + 2] = r_.z; } while (0)
+PTO_API void pto_normalize_array(const float *v, float *out, int n) { for (int i = 0; i < n; i++) PUT3(out, i, v_normalize(ROW3(v, i))); }
+PTO_API void pto_reflect_array(const float *in, const float *nr, float *out, int n) { for (int i = 0; i < n; i++) PUT3(out, i, f_reflect(ROW3(in, i), ROW3(nr, i))); }
+PTO_API void pto_refract_array(const float *in, const float *nr, const float *eta, float *out, int n)
+{ for (int i = 0; i < n; i++) PUT3(out, i, f_refract(ROW3(in, i), ROW3(nr, i), eta[i])); }
+PTO_API void pto_fresnel_schlick_array(const float *cosTheta, const float *n1, const float *n2, float *out, int n)
+{ for (int i = 0; i < n; i++) out[i] = fresnel_schlick(cosTheta[i], n1[i], n2[i]); }
+PTO_API void pto_cosine_sample_hemisphere_array(const float *nr, const uint32_t *seed, float *out, uint32_t *seed_out, int n)
+{ for (int i = 0; i < n; i++) { uint32_t s = seed[i]; PUT3(out, i, cosine_sample_hemisphere(ROW3(nr, i), &s)); seed_out[i] = s; } }
+PTO_API void pto_cuboid_normal_array(const float *mn, const float *mx, const float *p, float *out, int n)
+{ for (int i = 0; i < n; i++) PUT3(out, i, cuboid_normal(ROW3(mn, i), ROW3(mx, i), ROW3(p, i))); }
+#undef ROW3
+#undef PUT3
 
 /* ------------------------------------------------------------------ atmosphere precompute
  * res/shaders/AtmosphericScattering/compute.glsl:30-171 (algorithm credited there to

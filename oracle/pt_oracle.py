@@ -326,6 +326,98 @@ class Oracle:
     def sqrt(self, x):
         return self._array_fn("pto_sqrt_array", x)
 
+    # array forms of the other primitives and leaf functions: float32 / uint32 arrays in, arrays out, every row through memory as it is
+    def _rows(self, name, ins, outs, n, extra=()):
+        """pto_<name>_array(*ins, *extra-in-place, *outs, n): `ins` contiguous arrays, `outs` [(shape, dtype)]; `extra` = (position, ctypes value)"""
+        ins = [np.ascontiguousarray(a) for a in ins]
+        res = [np.empty(shape, dtype) for shape, dtype in outs]
+        args = [a.ctypes.data_as(C.c_void_p) for a in ins]
+        for pos, val in extra:
+            args.insert(pos, val)
+        args += [r.ctypes.data_as(C.c_void_p) for r in res]
+        fn = getattr(self.lib, f"pto_{name}_array")
+        fn.restype = None
+        fn.argtypes = [type(a) for a in args] + [C.c_int]
+        fn(*args, int(n))
+        return res[0] if len(res) == 1 else tuple(res)
+
+    @staticmethod
+    def _f32(*arrays):
+        return [np.ascontiguousarray(a, np.float32).reshape(-1) for a in arrays]
+
+    @staticmethod
+    def _vec3(*arrays):
+        return [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in arrays]
+
+    def mix_array(self, x, y, a):
+        x, y, a = self._f32(x, y, a)
+        return self._rows("mix", [x, y, a], [(x.shape, np.float32)], x.size)
+
+    def sincos_array(self, a):
+        (a,) = self._f32(a)
+        return self._rows("sincos", [a], [(a.shape, np.float32)] * 2, a.size)
+
+    def exp_array(self, x):
+        return self._array_fn("pto_exp_array", x)
+
+    def log_array(self, x):
+        return self._array_fn("pto_log_array", x)
+
+    def pow5_array(self, x):
+        return self._array_fn("pto_pow5_array", x)
+
+    def aces_film_array(self, x):
+        return self._array_fn("pto_aces_film_array", x)
+
+    def linear_to_inverse_gamma_array(self, v, gamma=2.4):
+        (v,) = self._f32(v)
+        return self._rows("linear_to_inverse_gamma", [v], [(v.shape, np.float32)], v.size, extra=[(1, C.c_float(gamma))])
+
+    def to_unorm8_array(self, v):
+        (v,) = self._f32(v)
+        return self._rows("to_unorm8", [v], [(v.shape, np.uint8)], v.size)
+
+    def pcg_hash_array(self, seeds):
+        """-> (words, seeds after the call)"""
+        s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        return self._rows("pcg_hash", [s], [(s.shape, np.uint32)] * 2, s.size)
+
+    def rand01_array(self, seeds):
+        """-> (values, seeds after the call)"""
+        s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        return self._rows("rand01", [s], [(s.shape, np.float32), (s.shape, np.uint32)], s.size)
+
+    def pixel_seed_array(self, xyf):
+        t = np.ascontiguousarray(xyf, np.int32).reshape(-1, 3)
+        return self._rows("pixel_seed", [t], [((len(t),), np.uint32)], len(t))
+
+    def normalize_array(self, v):
+        (v,) = self._vec3(v)
+        return self._rows("normalize", [v], [(v.shape, np.float32)], len(v))
+
+    def reflect_array(self, i, n):
+        i, n = self._vec3(i, n)
+        return self._rows("reflect", [i, n], [(i.shape, np.float32)], len(i))
+
+    def refract_array(self, i, n, eta):
+        i, n = self._vec3(i, n)
+        (eta,) = self._f32(eta)
+        return self._rows("refract", [i, n, eta], [(i.shape, np.float32)], len(i))
+
+    def fresnel_schlick_array(self, cos_theta, n1, n2):
+        c, n1, n2 = self._f32(cos_theta, n1, n2)
+        return self._rows("fresnel_schlick", [c, n1, n2], [(c.shape, np.float32)], c.size)
+
+    def cosine_sample_hemisphere_array(self, n, seeds):
+        """-> (directions, seeds after the call)"""
+        (n,) = self._vec3(n)
+        s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        return self._rows("cosine_sample_hemisphere", [n, s], [(n.shape, np.float32), (s.shape, np.uint32)], len(n))
+
+    def cuboid_normal_array(self, mn, mx, p):
+        mn, mx, p = self._vec3(mn, mx, p)
+        return self._rows("cuboid_normal", [mn, mx, p], [(p.shape, np.float32)], len(p))
+
     # ---------------------------------------------------------------- micro helpers
     def rand_stream(self, seed: int, n: int):
         s = C.c_uint32(seed)

@@ -125,6 +125,52 @@ def test_contract_reciprocal_root_accuracy(oracle):
     assert np.isnan(oracle.rsqrt(np.array([-1.0], np.float32)))[0]
 
 
+# Accuracy of the contract's sin / cos / exp / log on the domain grids of tests/math_probe_cases.py, against numpy float64.  The functions
+# are deterministic and the grids fixed and finite, so there is no noise margin: each bound is the measured maximum (beside it) rounded
+# up to the next 0.05.  sin and cos: absolute error in units of 2^-24; exp and log: float ulps.
+SIN_BOUND, SIN_MEASURED = 1.45, 1.41337  # (8.42e-8 absolute, at a = 0x40148767)
+COS_BOUND, COS_MEASURED = 1.60, 1.55098  # (9.24e-8 absolute, at a = 0x40175ae2)
+EXP_BOUND, EXP_MEASURED = 1.00, 0.99504  # (at x = 59.310074; 0.74609 over the denormal results)
+LOG_BOUND, LOG_MEASURED = 0.85, 0.80401  # (at x = 0.7003051)
+
+
+def test_contract_sincos_accuracy(oracle):
+    """every angle hemisphere_draws can form: a = (k 2^-24) * 2 * PI, k = 0 .. 2^24"""
+    import math_probe_cases as mc
+    a = mc.floats(mc.grid_d("pt_sincos")[:, 0])
+    s, c = oracle.sincos_array(a)
+    a64 = a.astype(np.float64)
+    es = np.abs(s.astype(np.float64) - np.sin(a64)).max() * 2.0 ** 24
+    ec = np.abs(c.astype(np.float64) - np.cos(a64)).max() * 2.0 ** 24
+    print(f"sin {es:.5f}, cos {ec:.5f} (units of 2^-24)")
+    assert es <= SIN_BOUND and ec <= COS_BOUND
+
+
+def test_contract_exp_accuracy(oracle):
+    """[-104, 88.73] with the floats around every threshold: wherever the exact value rounds to a finite float the result is within the
+    bound (denormal results included: 2^n is applied in two exact factors, so they are rounded once); wherever it rounds to infinity —
+    from x = 88.72283935546875 on — the result is infinity"""
+    import math_probe_cases as mc
+    x = mc.floats(mc.grid_d("pt_exp")[:, 0])
+    y = oracle.exp_array(x)
+    with np.errstate(over="ignore"):
+        exact = np.exp(x.astype(np.float64))
+        finite = np.isfinite(exact.astype(np.float32))
+    assert x[~finite].min() == np.float32(88.72283935546875) and np.isposinf(y[~finite]).all()
+    err = _ulp_error(y[finite], exact[finite])
+    print(f"exp {err.max():.5f} ulp; {err[exact[finite] < 1.17549435e-38].max():.5f} over the denormal results")
+    assert (exact[finite] < 1.17549435e-38).sum() > 50_000 and err.max() <= EXP_BOUND
+
+
+def test_contract_log_accuracy(oracle):
+    """[0.0031308, 1] (the arguments linear_to_inverse_gamma passes) with the floats around both ends"""
+    import math_probe_cases as mc
+    x = mc.floats(mc.grid_d("pt_log")[:, 0])
+    err = _ulp_error(oracle.log_array(x), np.log(x.astype(np.float64)))
+    print(f"log {err.max():.5f} ulp")
+    assert err.max() <= LOG_BOUND
+
+
 def test_thread_count_never_changes_the_image(oracle):
     """The row-parallel driver (oracle/pt_oracle.c, pto_render_frame) must render every row exactly once whatever thread count is
     asked for — more threads than rows (256 on the GPU box for an 8-row fuzz image), one thread, an odd count — and a worker that
