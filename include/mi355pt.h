@@ -520,6 +520,29 @@ PT_API int pt_denoise_read_noise(pt_handle h, float *dst, size_t row_pitch_bytes
  * three cases of pt_denoise_read_noise. */
 PT_API int pt_denoise_noise_level(pt_handle h, float *out_mean_variance, int *out_observations, int *out_hit_pixels);
 
+/* The adaptive sampler's noise as the denoiser's, for a host that shows the denoised image of MainWindow.cs:49-63
+ * while pt_adaptive_render (below) converges it.  An adaptively sampled image changes its noise level at every 8x8 tile border, and the
+ * moments above are refused on it; but every pixel of a live adaptive state carries an exact estimate e of its own noise, in Vm's unit.
+ * With the switch on, a pt_denoise_render in PT_DENOISE_VARIANCE with iterations > 0 on a live state reads, in pass 0, in place of V0:
+ * var_0 = ((k - k0) Et + prior_samples V0) / (k - k0 + prior_samples), where (k, k0) is the record of the pixel's own tile, Et = S / k
+ * and S = the mean of e(q) k_q over the pixels q of the same id in the 3x3 window, each with the count of its own tile — the window's
+ * per-sample variance, carried to the pixel's own count; var_0 = V0 on a miss and where k - k0 <= 0.  pt_denoise_read_variance still
+ * returns V0.  In every other case — no live state, PT_DENOISE_FIXED, iterations = 0 — the result is bit for bit what it is with the
+ * switch off.  Stream-ordered behind the passes already queued; reads the adaptive state and writes neither it nor the image.  The
+ * temporal stage and the moments stay refused on a live state. */
+
+/* Switch of the pt_denoise_render calls that follow — a GUI toggle's setter, like those MainWindow.cs:49-63 drives; the result is shown
+ * through ScreenEffect.cs:29-37; what is queued already keeps the values it was issued under.  enable: 0 or 1, anything else
+ * PT_E_BAD_ARGUMENT; prior_samples 1..65535 (how many samples the spatial estimate is worth in the blend), outside that
+ * PT_E_OUT_OF_RANGE; the previous values stay in force then.  Defaults 0, 8.  With enable = 0 pt_denoise_render is bit for bit what it
+ * was and allocates nothing.  Scope as for pt_denoise_set_params. */
+PT_API int pt_denoise_set_adaptive_noise(pt_handle h, int enable, int prior_samples);
+/* var_0 of the last pt_denoise_render — the variance its pass 0 read in place of V0, how noisy the filter took the image of
+ * MainWindow.cs:49-63 to be before the result went to ScreenEffect.cs:29-37, whether the switch above or pt_denoise_set_moments formed
+ * it — one float per pixel, rows like the image: blocks; row_pitch_bytes >= width*4, 0 = tightly packed.  PT_E_BAD_ARGUMENT when the last render blended nothing (pass 0 read V0: pt_denoise_read_variance), when
+ * nothing was rendered since the last (re)size / (re)tiling, for dst == NULL or a pitch smaller than a row. */
+PT_API int pt_denoise_read_variance_used(pt_handle h, float *dst, size_t row_pitch_bytes);
+
 /* ---- Adaptive sampling: per-tile sample counts driven by measured noise.  The reference spends every frame on every pixel
  * (PathTracer.cs:114-129); these entry points stop where the image is done and keep sampling where it is not.  The image is divided into
  * 8x8 tiles of the handle's own rows; every tile carries a record (k, k0, err, n): the samples its pixels hold, the count the statistics

@@ -400,6 +400,24 @@ static int denoise_run(pt_handle h, int guide_frame_index, int stage)
         PT_HIP(h, pt::launch_moments_blend(b, h->stream));
         d.blended = true;
     }
+    // stage A: on a live adaptive state (where stage M never ran: pt_denoise_render refuses the moments there) the sampler's own
+    // per-pixel estimate e and the tile records take Vm's place — stream-ordered behind the passes already queued, reading the state as
+    // they leave it and writing dVar0 only
+    if (stage == kDenoiseAll && d.adaptiveNoise && variance && n > 0 && !temporal && h->adaptiveLive() && h->adaptive.dTiles && h->adaptive.dStats) {
+        if (!d.dVar0) PT_HIP(h, hipMalloc((void **)&d.dVar0, pixels * sizeof(float)));
+        pt::AdaptiveBlendArgs b;
+        b.stats = h->adaptive.dStats;
+        b.tiles = h->adaptive.dTiles;
+        b.guides = guides;
+        b.v0 = d.dVariance;
+        b.var0 = d.dVar0;
+        b.width = h->width;
+        b.height = h->rows;
+        b.tilesX = h->tilesX();
+        b.k0 = (float)d.adaptivePrior;
+        PT_HIP(h, pt::launch_adaptive_blend(b, h->stream));
+        d.blended = true;
+    }
     const bool blended = d.blended && variance && !temporal && d.dVar0;
     for (int i = 0; i < n && stage != kDenoiseStageV; i++) {
         if (stage >= 0 && i != stage) continue;
@@ -636,6 +654,26 @@ PT_API int pt_denoise_noise_level(pt_handle h, float *out_mean_variance, int *ou
     if (out_observations) *out_observations = d.momentsK;
     if (out_hit_pixels) *out_hit_pixels = (int)count;
     return PT_OK;
+}
+
+PT_API int pt_denoise_set_adaptive_noise(pt_handle h, int enable, int prior_samples)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_owner(h)) return rc;
+    if (enable != 0 && enable != 1) return fail(h, PT_E_BAD_ARGUMENT, "enable must be 0 or 1");
+    if (prior_samples < 1 || prior_samples > 65535) return fail(h, PT_E_OUT_OF_RANGE, "prior_samples 1..65535");
+    h->denoise.adaptiveNoise = enable; // (read by the next pt_denoise_render; what is queued already took its values)
+    h->denoise.adaptivePrior = prior_samples;
+    return PT_OK;
+}
+
+PT_API int pt_denoise_read_variance_used(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = denoise_rendered(h)) return rc;
+    if (!h->denoise.blended)
+        return fail(h, PT_E_BAD_ARGUMENT, "the last pt_denoise_render blended no measured variance into pass 0's (pt_denoise_set_moments / pt_denoise_set_adaptive_noise)");
+    return denoise_copy_out(h, dst, row_pitch_bytes, h->denoise.dVar0, 4);
 }
 
 PT_API int pt_denoise_device_ptr(pt_handle h, void **out, size_t *bytes)

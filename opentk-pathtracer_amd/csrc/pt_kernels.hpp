@@ -326,6 +326,20 @@ struct AdaptiveArgs {
 hipError_t launch_adaptive(const FrameArgs &a, const AdaptiveArgs &ad, hipStream_t stream);
 // the records of a fresh state: (frame, max(frame, 1), +0, in-image pixels of the tile)
 hipError_t launch_adaptive_init(int4 *tiles, int tilesX, int tilesY, int width, int rows, int frame, hipStream_t stream);
+// the adaptive state as the denoiser's noise source (pt_denoise_set_adaptive_noise; pt_denoise_adaptive.hip).  Stage A:
+// var0 = ((jf Et) + (k0 v0)) / (jf + k0) with (k, k0) the record of the pixel's own tile, jf = (float)(k - k0), Et = S / (float)k, S = the
+// mean of e(q) (float)k_q over the pixels q of the centre's id in its 3x3 window; var0 = v0 where the id is -1 or k - k0 <= 0.  Reads the
+// state as the passes queued before it leave it and writes var0 only
+struct AdaptiveBlendArgs {
+    const float2 *stats;  // (M2, e) per pixel; M2 is not read
+    const int4 *tiles;    // tilesX x ceil(height / 8) records (k, k0, err bits, n); err and n are not read
+    const float4 *guides;
+    const float *v0;      // stage V's estimate
+    float *var0;          // width x height floats, compact rows
+    int width, height, tilesX; // tilesX = ceil(width / 8)
+    float k0;             // (float)prior_samples
+};
+hipError_t launch_adaptive_blend(const AdaptiveBlendArgs &a, hipStream_t stream);
 hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 // the same cube in the reference arithmetic (pt_integrate_reference.hip, pt_atmosphere_reference.hpp)
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);

@@ -256,6 +256,9 @@ struct pt_renderer {
         long long momentsN = 0;
         unsigned long long momentsEpoch = 0;
         bool noiseValid = false, blended = false;
+        // The adaptive sampler's noise (pt_denoise_set_adaptive_noise; pt_denoise_adaptive.hip): on a live adaptive state stage A forms
+        // var_0 in dVar0 from the state's (e, records) and sets `blended` as stage B does; it allocates dVar0 where it runs first.
+        int adaptiveNoise = 0, adaptivePrior = 8;
 
         bool allocated() const
         {

@@ -455,6 +455,17 @@ public:
         Check(pt_adaptive_read_noise(h_, noise.data(), 0), h_);
         return noise;
     }
+    // the adaptive sampler's noise for the Denoise() calls that follow: on a live adaptive state PT_DENOISE_VARIANCE forms pass 0's variance
+    // from the per-pixel estimate and the tile counts, blended with the spatial estimate, worth priorSamples (1..65535) samples
+    void SetDenoiseAdaptiveNoise(bool enable = true, int priorSamples = 8) { Check(pt_denoise_set_adaptive_noise(h_, enable ? 1 : 0, priorSamples), h_); }
+    // the variance pass 0 of the last Denoise() read in place of the spatial estimate (from the adaptive state or the moments): one float
+    // per pixel, row 0 = bottom; fails when that Denoise() blended nothing
+    std::vector<float> DenoiseVarianceUsed() const
+    {
+        std::vector<float> var((size_t)width_ * height_);
+        Check(pt_denoise_read_variance_used(h_, var.data(), 0), h_);
+        return var;
+    }
     // ScreenEffect.Render (src/Render/ScreenEffect.cs:29-37) of the last Denoise() instead of `Result`
     std::vector<uint8_t> PresentDenoised() const
     {

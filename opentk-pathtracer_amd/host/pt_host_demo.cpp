@@ -98,6 +98,9 @@ int main(int argc, char **argv)
             if (argc > 6) pathTracer.SetDenoise(std::atoi(argv[6]));
             const bool varianceGuided = argc > 7 && std::atof(argv[7]) > 0.0;
             if (varianceGuided) pathTracer.SetDenoiseMode(PT_DENOISE_VARIANCE, (float)std::atof(argv[7]));
+            // what a host that goes on with RenderAdaptive() sets once: from then on the filter reads the sampler's own per-pixel noise
+            // (with Render() alone, as here, there is no adaptive state and nothing changes)
+            if (varianceGuided) pathTracer.SetDenoiseAdaptiveNoise();
             std::vector<uint8_t> shown;
             for (int i = 0; i < frames; i++) {
                 pathTracer.Render();                  // OnRenderFrame, MainWindow.cs:49

@@ -434,6 +434,19 @@ class PathTracer:
         check(self._lib.pt_adaptive_read_noise(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
         return out
 
+    def SetDenoiseAdaptiveNoise(self, enable: bool = True, prior_samples: int = 8) -> None:
+        """pt_denoise_set_adaptive_noise: on a live adaptive state the Denoise calls that follow form pass 0's variance in
+        PT_DENOISE_VARIANCE from the sampler's own per-pixel estimate e and the tile counts, blended with the spatial estimate, which
+        counts as prior_samples (1..65535) samples.  Without a live state nothing changes."""
+        check(self._lib.pt_denoise_set_adaptive_noise(self._h, int(enable), prior_samples), self._h)
+
+    def DenoiseVarianceUsed(self) -> np.ndarray:
+        """pt_denoise_read_variance_used: var_0, the variance pass 0 of the last Denoise read in place of V0 (formed from the adaptive
+        state or from the moments), as (rows, Width) float32; raises when that Denoise blended nothing."""
+        out = np.empty((self.rows, self.Width), dtype=np.float32)
+        check(self._lib.pt_denoise_read_variance_used(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
+        return out
+
     def PresentDenoised(self) -> np.ndarray:
         """pt_denoise_present_rgba8: the result of the last Denoise through the tone map Present applies, as (rows, Width, 4) uint8."""
         out = np.empty((self.rows, self.Width, 4), dtype=np.uint8)
