@@ -555,7 +555,9 @@ PT_API int pt_denoise_read_variance_used(pt_handle h, float *dst, size_t row_pit
  * While an adaptive state is LIVE — from the pt_adaptive_render that initialises it until pt_reset, pt_write_result, pt_set_size,
  * pt_set_tile, pt_set_interleaved_tile or pt_bind_result_buffer — pixels hold different sample counts: pt_get_frame_index keeps returning
  * the frame index F the state started from, pt_render and a pt_denoise_render with the temporal stage or the moments on return
- * PT_E_BAD_ARGUMENT and touch nothing; everything that only reads the image works unchanged.  A host that never calls
+ * PT_E_BAD_ARGUMENT and touch nothing, until pt_reset or pt_adaptive_end; everything that only reads the image works unchanged.  A live
+ * state can be saved and restored (pt_adaptive_read_m2, pt_adaptive_write_state) and left without losing the image (pt_adaptive_end).  A
+ * host that never calls
  * pt_adaptive_render is not affected in any way.  Single-GPU handles, under pt_set_tile / pt_set_interleaved_tile too; a group handle:
  * PT_E_BAD_ARGUMENT. */
 
@@ -580,6 +582,26 @@ PT_API int pt_adaptive_read_tiles(pt_handle h, void *dst_16_bytes_per_tile);
 /* Blocks.  The per-pixel estimate e (the heat map a GUI would show), one float per pixel, rows like the image; row_pitch_bytes >=
  * width*4, 0 = tightly packed.  PT_E_BAD_ARGUMENT without a live state, for dst == NULL or a pitch smaller than a row. */
 PT_API int pt_adaptive_read_noise(pt_handle h, float *dst, size_t row_pitch_bytes);
+/* Blocks.  The per-pixel Welford sum M2, laid out like pt_adaptive_read_noise's map, with the same refusals.  With pt_read_result,
+ * pt_get_frame_index (F) and pt_adaptive_read_tiles this is the whole state: e and err are functions of these. */
+PT_API int pt_adaptive_read_m2(pt_handle h, float *dst, size_t row_pitch_bytes);
+/* Blocks.  Installs a live state: the image and frame index F as pt_write_result(image, F) installs them (alpha forced to 1, a new reset
+ * epoch), the records' (k, k0, n) and M2 as given, e and err rebuilt from them bit for bit as the pass that left the state wrote them.
+ * From here every read-out and every later pass equals those of the handle the state was read from, given the same inputs.  Everything
+ * is checked first, and a refused call touches nothing — not the image, the frame index, the reset epoch nor a live state:
+ * PT_E_BAD_ARGUMENT for a NULL pointer, a pitch smaller than a row (0 = tightly packed) or frame_index < 0; PT_E_OUT_OF_RANGE unless
+ * every record has n = the tile's in-image pixel count, k0 = max(frame_index, 1) and frame_index <= k <= 65535.  err in the records is
+ * not read; M2 is taken as bits (any float).  Needs neither an environment nor the contract arithmetic: the next pt_adaptive_render
+ * makes its own checks.  The buffers are allocated if the handle has none. */
+PT_API int pt_adaptive_write_state(pt_handle h, const float *image_rgba32f, size_t image_pitch_bytes, int frame_index,
+                                   const void *tiles_16_bytes_per_tile, const float *m2, size_t m2_pitch_bytes);
+/* Levels and leaves: with kmax / kmin the largest / smallest k of the records, enqueues kmax - kmin passes in which exactly the tiles
+ * with k < kmax are active (the pt_adaptive_set_params values are neither read nor changed), ends the state as pt_bind_result_buffer ends
+ * it — no new reset epoch: the accumulation continues — and sets the frame index to kmax (*out_frame_index, may be NULL).  The image then
+ * equals kmax pt_render frames bit for bit; pt_render, the temporal stage and the moments are accepted again.  Blocks only to fetch the
+ * records.  PT_E_BAD_ARGUMENT without a live state; when passes are needed (kmin < kmax) pt_adaptive_render's preconditions apply with
+ * its error codes, and a refused call touches nothing.  A state that never diverged ends without a launch. */
+PT_API int pt_adaptive_end(pt_handle h, int *out_frame_index);
 
 PT_API const char *pt_last_error(pt_handle h);
 PT_API const char *pt_version(void);

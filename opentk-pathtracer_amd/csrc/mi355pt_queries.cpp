@@ -831,6 +831,108 @@ PT_API int pt_adaptive_read_noise(pt_handle h, float *dst, size_t row_pitch_byte
     return adaptive_copy_stat(h, dst, row_pitch_bytes, 1);
 }
 
+PT_API int pt_adaptive_read_m2(pt_handle h, float *dst, size_t row_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_live(h)) return rc;
+    return adaptive_copy_stat(h, dst, row_pitch_bytes, 0);
+}
+
+// A live state installed from its persistent half — the image, F, (k, k0, n) per tile, M2 per pixel; e and err are rebuilt
+// (pt_adaptive_state.hip).  Everything is checked before anything of the handle is touched.
+PT_API int pt_adaptive_write_state(pt_handle h, const float *image_rgba32f, size_t image_pitch_bytes, int frame_index, const void *tiles_16_bytes_per_tile,
+                                   const float *m2, size_t m2_pitch_bytes)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_owner(h)) return rc;
+    if (!image_rgba32f || !tiles_16_bytes_per_tile || !m2 || frame_index < 0)
+        return fail(h, PT_E_BAD_ARGUMENT, "image == NULL, tiles == NULL, m2 == NULL or negative frame index");
+    if (h->rows < 1 || h->width < 1) return fail(h, PT_E_BAD_ARGUMENT, "the handle owns no rows");
+    if (h->boundAccum && h->boundBytes < h->tilePixels() * sizeof(float4))
+        return fail(h, PT_E_BAD_ARGUMENT, "bound result buffer is smaller than the tile");
+    const size_t m2RowBytes = (size_t)h->width * 4;
+    if (m2_pitch_bytes == 0) m2_pitch_bytes = m2RowBytes;
+    if ((image_pitch_bytes != 0 && image_pitch_bytes < (size_t)h->width * 16) || m2_pitch_bytes < m2RowBytes)
+        return fail(h, PT_E_BAD_ARGUMENT, "row pitch smaller than a row");
+    const int tilesX = h->tilesX(), tilesY = h->tilesY();
+    std::vector<int4> rec((size_t)tilesX * tilesY);
+    std::memcpy(rec.data(), tiles_16_bytes_per_tile, rec.size() * sizeof(int4));
+    const int k0 = frame_index > 1 ? frame_index : 1;
+    for (int t = 0; t < tilesX * tilesY; t++) {
+        const int tx = t % tilesX, ty = t / tilesX;
+        const int w = h->width - tx * 8 < 8 ? h->width - tx * 8 : 8, r = h->rows - ty * 8 < 8 ? h->rows - ty * 8 : 8;
+        int4 &q = rec[(size_t)t];
+        if (q.w != w * r || q.y != k0 || q.x < frame_index || q.x > 65535)
+            return fail(h, PT_E_OUT_OF_RANGE, "tile record: n = the tile's in-image pixels, k0 = max(frame_index, 1), frame_index <= k <= 65535");
+        q.z = 0; // (err is not read: the rebuild writes it)
+    }
+    std::vector<float2> st(h->tilePixels());
+    for (int y = 0; y < h->rows; y++) {
+        const float *row = (const float *)((const unsigned char *)m2 + (size_t)y * m2_pitch_bytes);
+        float2 *out = st.data() + (size_t)y * h->width;
+        for (int x = 0; x < h->width; x++) {
+            std::memcpy(&out[x].x, row + x, 4); // (as bits: any float)
+            out[x].y = 0.0f;
+        }
+    }
+    // the image: what pt_write_result does — join, upload, alpha = 1, the frame index, a new reset epoch (whatever state was live ends here)
+    if (int rc = pt_write_result(h, image_rgba32f, image_pitch_bytes, frame_index)) return rc;
+    pt_renderer::Adaptive &ad = h->adaptive;
+    if (!ad.dTiles) PT_HIP(h, hipMalloc((void **)&ad.dTiles, rec.size() * sizeof(int4)));
+    if (!ad.dStats) PT_HIP(h, hipMalloc((void **)&ad.dStats, st.size() * sizeof(float2)));
+    PT_HIP(h, hipMemcpyAsync(ad.dTiles, rec.data(), rec.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+    PT_HIP(h, hipMemcpyAsync(ad.dStats, st.data(), st.size() * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    pt::AdaptiveRebuildArgs a;
+    a.image = h->accum();
+    a.stats = ad.dStats;
+    a.tiles = ad.dTiles;
+    a.width = h->width;
+    a.rows = h->rows;
+    a.tilesX = tilesX;
+    a.tilesY = tilesY;
+    PT_HIP(h, pt::launch_adaptive_rebuild(a, h->stream));
+    PT_HIP(h, hipStreamSynchronize(h->stream)); // (the uploads read this call's own vectors)
+    ad.started = true;
+    ad.epoch = h->resetEpoch;
+    return PT_OK;
+}
+
+// Levels every tile to the largest count with the sampler's own kernel — under (threshold 0, min 65535, max kmax) a tile is active exactly
+// while k < kmax, since k - k0 < 65534 for every k < 65535 — and leaves the state as pt_bind_result_buffer leaves it: the image then holds
+// kmax uniform frames in every pixel, so the accumulation goes on with frame index kmax in the same reset epoch.
+PT_API int pt_adaptive_end(pt_handle h, int *out_frame_index)
+{
+    PT_CHECK_HANDLE(h);
+    if (int rc = adaptive_live(h)) return rc;
+    std::vector<int4> rec;
+    if (int rc = adaptive_fetch_tiles(h, rec)) return rc;
+    int lo = rec[0].x, hi = rec[0].x;
+    for (const int4 &r : rec) {
+        lo = r.x < lo ? r.x : lo;
+        hi = r.x > hi ? r.x : hi;
+    }
+    if (lo < hi) {
+        if (h->arithmetic != PT_ARITH_CONTRACT) return fail(h, PT_E_BAD_ARGUMENT, "adaptive sampling renders in the contract arithmetic only (pt_set_arithmetic)");
+        if (!h->dEnv) return fail(h, PT_E_NO_ENVIRONMENT, "pt_adaptive_end called before pt_set_environment / pt_atmosphere_render");
+        if (h->boundAccum && h->boundBytes < h->tilePixels() * sizeof(float4))
+            return fail(h, PT_E_BAD_ARGUMENT, "bound result buffer is smaller than the tile");
+        if (int rc = ptimpl::fix_alpha(h)) return rc;
+        pt::FrameArgs a;
+        if (int rc = ptimpl::plain_frame_args(h, a, h->frame)) return rc;
+        pt::AdaptiveArgs p;
+        p.tiles = h->adaptive.dTiles;
+        p.stats = h->adaptive.dStats;
+        p.threshold = 0.0f; // (the host's pt_adaptive_set_params values are neither read nor changed)
+        p.minSamples = 65535;
+        p.maxSamples = hi;
+        for (int i = lo; i < hi; i++) PT_HIP(h, pt::launch_adaptive(a, p, h->stream));
+    }
+    h->adaptive.started = false;
+    h->frame = hi;
+    if (out_frame_index) *out_frame_index = hi;
+    return PT_OK;
+}
+
 // Test aid (not declared in the public header): the per-pixel M2 of the adaptive state, laid out like pt_adaptive_read_noise's map.
 extern "C" __attribute__((visibility("default"))) int pt_debug_adaptive_read_m2(pt_handle h, float *dst, size_t row_pitch_bytes)
 {

@@ -326,6 +326,16 @@ struct AdaptiveArgs {
 hipError_t launch_adaptive(const FrameArgs &a, const AdaptiveArgs &ad, hipStream_t stream);
 // the records of a fresh state: (frame, max(frame, 1), +0, in-image pixels of the tile)
 hipError_t launch_adaptive_init(int4 *tiles, int tilesX, int tilesY, int width, int rows, int frame, hipStream_t stream);
+// a restored adaptive state completed (pt_adaptive_write_state; pt_adaptive_state.hip): from the image, stats[p].x = M2 and
+// the records' (k, k0, n) as uploaded, writes stats[p].y = e (steps 4 of the definition with kNext = k; 0 while k - k0 < 1) and every
+// record's err (step 5).  tilesX x tilesY = ceil(width / 8) x ceil(rows / 8) records; image and stats hold rows x width pixels
+struct AdaptiveRebuildArgs {
+    const float4 *image;
+    float2 *stats;
+    int4 *tiles;
+    int width, rows, tilesX, tilesY;
+};
+hipError_t launch_adaptive_rebuild(const AdaptiveRebuildArgs &a, hipStream_t stream);
 // the adaptive state as the denoiser's noise source (pt_denoise_set_adaptive_noise; pt_denoise_adaptive.hip).  Stage A:
 // var0 = ((jf Et) + (k0 v0)) / (jf + k0) with (k, k0) the record of the pixel's own tile, jf = (float)(k - k0), Et = S / (float)k, S = the
 // mean of e(q) (float)k_q over the pixels q of the centre's id in its 3x3 window; var0 = v0 where the id is -1 or k - k0 <= 0.  Reads the

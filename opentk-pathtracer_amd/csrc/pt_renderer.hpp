@@ -297,6 +297,8 @@ struct pt_renderer {
     // of the handle's rows, dStats = (M2, e) per pixel; both allocated by the first pt_adaptive_render after a (re)size or (re)tiling and
     // freed by the next one — never on the pt_render path.  The state is LIVE from the pt_adaptive_render that initialises it until the
     // reset epoch changes or pt_bind_result_buffer is called: pixels then hold different sample counts, `frame` stays what it was.
+    // pt_adaptive_write_state installs a live state from its persistent half (pt_adaptive_state.hip rebuilds e and err) and allocates the
+    // buffers likewise; pt_adaptive_end levels the tiles, ends the state in the same epoch and moves `frame` to the common count.
     struct Adaptive {
         int4 *dTiles = nullptr;
         float2 *dStats = nullptr;

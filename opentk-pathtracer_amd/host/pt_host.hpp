@@ -430,13 +430,21 @@ public:
     }
     // Adaptive sampling: per-tile sample counts driven by measured noise.  A tile stays active while it holds fewer than maxSamples samples
     // and either fewer than minSamples since its statistics started or a noise estimate above threshold
-    void SetAdaptive(float threshold = 1e-4f, int minSamples = 8, int maxSamples = 1024) { Check(pt_adaptive_set_params(h_, threshold, minSamples, maxSamples), h_); }
+    struct AdaptiveParameters { float threshold = 1e-4f; int minSamples = 8, maxSamples = 1024; };
+    void SetAdaptive(float threshold = 1e-4f, int minSamples = 8, int maxSamples = 1024)
+    {
+        Check(pt_adaptive_set_params(h_, threshold, minSamples, maxSamples), h_);
+        adaptive_ = AdaptiveParameters{threshold, minSamples, maxSamples};
+    }
+    // the values of the last successful SetAdaptive (what a checkpoint of a live state stores beside it)
+    AdaptiveParameters AdaptiveParams() const { return adaptive_; }
     // `passes` passes, each one more sample per pixel of every tile still active (asynchronous); until ResetRenderer(), Render() fails
     void RenderAdaptive(int passes = 1) { Check(pt_adaptive_render(h_, passes), h_); }
     struct AdaptiveState { int activeTiles, tiles; int64_t pixelSamples; int minCount, maxCount; };
-    AdaptiveState AdaptiveStatus() const
+    // (the struct shares its name with the member AdaptiveState() below: name it `struct AdaptiveState`, or let `auto` do it)
+    struct AdaptiveState AdaptiveStatus() const
     {
-        AdaptiveState s{};
+        struct AdaptiveState s{};
         Check(pt_adaptive_status(h_, &s.activeTiles, &s.tiles, &s.pixelSamples, &s.minCount, &s.maxCount), h_);
         return s;
     }
@@ -455,6 +463,34 @@ public:
         Check(pt_adaptive_read_noise(h_, noise.data(), 0), h_);
         return noise;
     }
+    // the per-pixel Welford sum M2: one float per pixel, row 0 = bottom
+    std::vector<float> AdaptiveM2() const
+    {
+        std::vector<float> m2((size_t)width_ * height_);
+        Check(pt_adaptive_read_m2(h_, m2.data(), 0), h_);
+        return m2;
+    }
+    // whether an adaptive state is live (pt_adaptive_status with every pointer NULL returns PT_OK); never throws
+    bool AdaptiveLive() const { return pt_adaptive_status(h_, nullptr, nullptr, nullptr, nullptr, nullptr) == PT_OK; }
+    // the whole of a live state: the frame index it started from, the image, the tile records and M2 — the per-pixel estimate and the
+    // tiles' err are functions of these, and RestoreAdaptive rebuilds them
+    struct AdaptiveSnapshot { int frameIndex; std::vector<float> image; std::vector<AdaptiveTile> tiles; std::vector<float> m2; };
+    AdaptiveSnapshot AdaptiveState() const
+    {
+        AdaptiveSnapshot s;
+        Check(pt_get_frame_index(h_, &s.frameIndex), h_);
+        s.image = Result();
+        s.tiles = AdaptiveTiles();
+        s.m2 = AdaptiveM2();
+        return s;
+    }
+    // installs a live state as AdaptiveState() returned it (tightly packed rows); every read-out and every later pass then equals those of
+    // the renderer it was read from; a refused call changes nothing
+    void RestoreAdaptive(const float *image, int frameIndex, const AdaptiveTile *tiles, const float *m2) { Check(pt_adaptive_write_state(h_, image, 0, frameIndex, tiles, m2, 0), h_); }
+    void RestoreAdaptive(const AdaptiveSnapshot &s) { RestoreAdaptive(s.image.data(), s.frameIndex, s.tiles.data(), s.m2.data()); }
+    // levels every tile to the largest count and leaves the adaptive state: the image then equals that many Render() calls bit for bit and
+    // Render() is accepted again; returns the new frame index
+    int EndAdaptive() { int f = 0; Check(pt_adaptive_end(h_, &f), h_); return f; }
     // the adaptive sampler's noise for the Denoise() calls that follow: on a live adaptive state PT_DENOISE_VARIANCE forms pass 0's variance
     // from the per-pixel estimate and the tile counts, blended with the spatial estimate, worth priorSamples (1..65535) samples
     void SetDenoiseAdaptiveNoise(bool enable = true, int priorSamples = 8) { Check(pt_denoise_set_adaptive_noise(h_, enable ? 1 : 0, priorSamples), h_); }
@@ -546,6 +582,7 @@ private:
     int numSpheres_ = 0, numCuboids_ = 0, rayDepth_, spp_;
     float focalLength_, apertureDiameter_;
     int width_, height_;
+    AdaptiveParameters adaptive_; // the last SetAdaptive values (the library's defaults; the ABI has no getter)
 };
 
 // ---- AtmosphericScatterer (src/Render/AtmosphericScatterer.cs:9-119); its Result becomes the tracer's environment

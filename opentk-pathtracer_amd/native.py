@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("MI355PT_LIB") or os.path.join(HERE, "libmi355pt.so")  # MI355PT_LIB: A/B tuning builds
 HEADER = os.path.join(REPO, "include", "mi355pt.h")
 SOURCES = ["pt_integrate_persistent.hip", "pt_integrate_multisample.hip", "pt_integrate_reference.hip", "pt_first_hit.hip", "pt_denoise.hip",
-           "pt_denoise_moments.hip", "pt_adaptive.hip", "pt_denoise_adaptive.hip", "pt_helper_kernels.hip", "mi355pt.cpp", "mi355pt_launch.cpp", "mi355pt_handover.cpp",
+           "pt_denoise_moments.hip", "pt_adaptive.hip", "pt_adaptive_state.hip", "pt_denoise_adaptive.hip", "pt_helper_kernels.hip", "mi355pt.cpp", "mi355pt_launch.cpp", "mi355pt_handover.cpp",
            "mi355pt_present.cpp", "mi355pt_debug.cpp", "mi355pt_queries.cpp", "mi355pt_multi.cpp"]
 # -ffp-contract=off / -fno-fast-math are part of the pt-f32 arithmetic contract (csrc/pt_math.hpp)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-shared",
@@ -268,6 +268,9 @@ def load() -> C.CDLL:
         "pt_adaptive_status": [vp, ip, ip, C.POINTER(C.c_int64), ip, ip],
         "pt_adaptive_read_tiles": [vp, vp],
         "pt_adaptive_read_noise": [vp, fp, C.c_size_t],
+        "pt_adaptive_read_m2": [vp, fp, C.c_size_t],
+        "pt_adaptive_write_state": [vp, fp, C.c_size_t, C.c_int, vp, fp, C.c_size_t],
+        "pt_adaptive_end": [vp, ip],
         "pt_denoise_set_adaptive_noise": [vp, C.c_int, C.c_int],
         "pt_denoise_read_variance_used": [vp, fp, C.c_size_t],
     }

@@ -85,6 +85,7 @@ class PathTracer:
         self._rayDepth, self._spp = rayDepth, spp
         self._focalLength, self._apertureDiameter = focalLength, apertureDiamater
         self._push_params()
+        self._adaptive = (1e-4, 8, 1024)  # the last SetAdaptive values (the library's defaults; the ABI has no getter)
         self._env = None
         self.BasicDataUBO = UniformBuffer(self, "basic")       # MainWindow.cs:195-197
         self.GameObjectsUBO = UniformBuffer(self, "objects")   # MainWindow.cs:199-201
@@ -410,6 +411,12 @@ class PathTracer:
         """pt_adaptive_set_params: a tile stays active while it holds fewer than max_samples samples and either fewer than min_samples
         since its statistics started or a noise estimate (variance of the tone-compressed luminance) above threshold."""
         check(self._lib.pt_adaptive_set_params(self._h, threshold, min_samples, max_samples), self._h)
+        self._adaptive = (float(np.float32(threshold)), int(min_samples), int(max_samples))
+
+    @property
+    def AdaptiveParams(self) -> tuple:
+        """(threshold, min_samples, max_samples) as the last successful SetAdaptive left them (the defaults before the first)."""
+        return self._adaptive
 
     def RenderAdaptive(self, passes: int = 1) -> None:
         """pt_adaptive_render: `passes` passes, each one more sample per pixel of every tile still active.  Asynchronous.  The first call
@@ -433,6 +440,41 @@ class PathTracer:
         out = np.empty((self.rows, self.Width), dtype=np.float32)
         check(self._lib.pt_adaptive_read_noise(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
         return out
+
+    def AdaptiveM2(self) -> np.ndarray:
+        """pt_adaptive_read_m2: the per-pixel Welford sum M2 as (rows, Width) float32."""
+        out = np.empty((self.rows, self.Width), dtype=np.float32)
+        check(self._lib.pt_adaptive_read_m2(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), 0), self._h)
+        return out
+
+    @property
+    def AdaptiveLive(self) -> bool:
+        """Whether an adaptive state is live (pt_adaptive_status with every pointer NULL returns PT_OK).  Never raises."""
+        return self._lib.pt_adaptive_status(self._h, None, None, None, None, None) == native.PT_OK
+
+    def AdaptiveState(self) -> dict:
+        """The whole of a live state: frame_index (the F it started from), image, tiles (ADAPTIVE_TILE_DTYPE), m2.  The per-pixel
+        estimate and the tiles' err are functions of these; RestoreAdaptive rebuilds them."""
+        return {"frame_index": self.FrameIndex, "image": self.Result, "tiles": self.AdaptiveTiles(), "m2": self.AdaptiveM2()}
+
+    def RestoreAdaptive(self, image: np.ndarray, frame_index: int, tiles: np.ndarray, m2: np.ndarray) -> None:
+        """pt_adaptive_write_state: installs a live state as AdaptiveState returned it; every read-out and every later pass then equals
+        those of the tracer the state was read from.  A refused call changes nothing."""
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        rec = np.ascontiguousarray(tiles, dtype=ADAPTIVE_TILE_DTYPE)
+        sums = np.ascontiguousarray(m2, dtype=np.float32)
+        assert img.shape == (self.rows, self.Width, 4) and sums.shape == (self.rows, self.Width)
+        assert rec.shape == ((self.rows + 7) // 8, (self.Width + 7) // 8)
+        fp = C.POINTER(C.c_float)
+        check(self._lib.pt_adaptive_write_state(self._h, img.ctypes.data_as(fp), 0, frame_index, rec.ctypes.data_as(C.c_void_p),
+                                                sums.ctypes.data_as(fp), 0), self._h)
+
+    def EndAdaptive(self) -> int:
+        """pt_adaptive_end: levels every tile to the largest count and leaves the adaptive state; the image then equals that many Render
+        calls bit for bit and Render is accepted again.  -> the new frame index."""
+        v = C.c_int()
+        check(self._lib.pt_adaptive_end(self._h, C.byref(v)), self._h)
+        return v.value
 
     def SetDenoiseAdaptiveNoise(self, enable: bool = True, prior_samples: int = 8) -> None:
         """pt_denoise_set_adaptive_noise: on a live adaptive state the Denoise calls that follow form pass 0's variance in
