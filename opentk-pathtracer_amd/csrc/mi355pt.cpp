@@ -184,8 +184,10 @@ PT_API int pt_create(int device_id, int width, int height, pt_handle *out)
     PT_CREATE_HIP(hipStreamCreateWithFlags(&h->copyStream, hipStreamNonBlocking));
     PT_CREATE_HIP(hipEventCreate(&h->evBegin));
     PT_CREATE_HIP(hipEventCreate(&h->evEnd));
-    PT_CREATE_HIP(hipMalloc((void **)&h->dObjects, PT_GAME_OBJECTS_UBO_SIZE));
-    PT_CREATE_HIP(hipMemsetAsync(h->dObjects, 0, PT_GAME_OBJECTS_UBO_SIZE, h->stream));
+    // (UBO 1 and, behind it, the packed sphere geometry the scalar sphere step reads: pt_kernels.hpp, kSphereGeomOffset)
+    static_assert(pt::kSphereGeomOffset == PT_GAME_OBJECTS_UBO_SIZE && pt::kSphereGeomEntries == PT_MAX_SPHERES, "sphereGeom follows UBO 1");
+    PT_CREATE_HIP(hipMalloc((void **)&h->dObjects, PT_GAME_OBJECTS_UBO_SIZE + PT_MAX_SPHERES * 16));
+    PT_CREATE_HIP(hipMemsetAsync(h->dObjects, 0, PT_GAME_OBJECTS_UBO_SIZE + PT_MAX_SPHERES * 16, h->stream));
     PT_CREATE_HIP(hipMalloc((void **)&h->dGrid, (ptgrid::kMaxCells + 1) * 2 + ptgrid::kMaxRefs + 16));
     PT_CREATE_HIP(hipMalloc((void **)&h->dLut, 256 * sizeof(float)));
     PT_CREATE_HIP(hipMalloc((void **)&h->dQueue, ptimpl::kQueueWords * sizeof(unsigned int)));
@@ -434,10 +436,17 @@ PT_API int pt_upload_game_objects(pt_handle h, int byte_offset, int size, const 
     if (int rc = join_stripes(h)) return rc;
     // pageable source: HIP stages the bytes before returning, so the caller may reuse `src` immediately
     PT_HIP(h, hipMemcpyAsync((char *)h->dObjects + byte_offset, src, (size_t)size, hipMemcpyHostToDevice, h->stream));
+    // (the device block holds the new bytes from here on: shadow and flags follow it before anything else can fail)
     std::memcpy(h->objectsShadow + byte_offset, src, (size_t)size);
     if (byte_offset < PT_MAX_SPHERES * 80) h->gridDirty = true; // (the Spheres[] array ends at byte 20,480)
     h->masks.tileMasksValid = false; // (any object: the cached per-tile masks hold a sphere mask and a cuboid mask)
     h->masks.launchesSinceInputChange = 0;
+    {
+        // the packed sphere geometry follows on the same stream: whatever is ordered against the copy is ordered against the refresh
+        int first, count;
+        pt::sphere_geom_range(byte_offset, size, first, count);
+        PT_HIP(h, pt::launch_sphere_geom(h->dObjects, first, count, h->stream));
+    }
     return PT_OK;
 }
 

@@ -134,6 +134,31 @@ extern "C" __attribute__((visibility("default"))) int pt_debug_sphere_runs(const
     return PT_OK;
 }
 
+// Test aid (not declared in the public header; needs no GPU): the spheres whose packed geometry (pt_kernels.hpp, sphereGeom) an upload of
+// [byte_offset, byte_offset + size) into the GameObjectsUBO refreshes — pt::sphere_geom_range, the function pt_upload_game_objects uses.
+// out[0] = first sphere, out[1] = count (0: none).
+extern "C" __attribute__((visibility("default"))) int pt_debug_sphere_geom_range(int byte_offset, int size, int out[2])
+{
+    if (!out) return PT_E_BAD_ARGUMENT;
+    pt::sphere_geom_range(byte_offset, size, out[0], out[1]);
+    return PT_OK;
+}
+
+// Test aid (not declared in the public header): the device's UBO 1 (objects_out, PT_GAME_OBJECTS_UBO_SIZE bytes, may be null) and the packed
+// sphere geometry behind it (geom_out, 256 x 4 floats, may be null) of part `part` of a group handle (0 for a plain handle), read behind
+// everything queued on the handle's stream.
+extern "C" __attribute__((visibility("default"))) int pt_debug_read_sphere_geom(pt_handle h, int part, void *objects_out, float *geom_out)
+{
+    PT_CHECK_HANDLE(h);
+    if (h->isGroup() ? (part < 0 || part >= (int)h->group.parts.size()) : part != 0) return fail(h, PT_E_BAD_ARGUMENT, "no such part");
+    pt_handle r = h->isGroup() ? h->group.parts[(size_t)part] : h;
+    if (int rc = bind_device(r)) return rc;
+    PT_HIP(h, hipStreamSynchronize(r->stream));
+    if (objects_out) PT_HIP(h, hipMemcpy(objects_out, r->dObjects, PT_GAME_OBJECTS_UBO_SIZE, hipMemcpyDeviceToHost));
+    if (geom_out) PT_HIP(h, hipMemcpy(geom_out, (const char *)r->dObjects + pt::kSphereGeomOffset, (size_t)pt::kSphereGeomEntries * 16, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 // Test aid (not declared in the public header; needs no GPU): what launch_integrate would decide (pt::plan_launch) for a launch with
 // these arguments and these values of the kernel-selection knobs.  The process-wide knobs are not consulted and nothing is launched.
 // kernelRow: the row of the family's dispatch table the plan names (-1: none, or a family without a table).

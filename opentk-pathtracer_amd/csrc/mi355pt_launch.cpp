@@ -110,7 +110,7 @@ int fill_frame_args(pt_handle h, pt::FrameArgs &a, int firstFrame, int n)
     a.batchFrames = n;
     a.envSize = h->envSize;
     a.envFormat = h->envFormat;
-    a.objects = h->dObjects;
+    a.objects = h->dObjects; // (the block AND sphereGeom behind it, pt_kernels.hpp kSphereGeomOffset: `objects` always names an allocation of 26,624 + 4,096 bytes)
     a.env = h->dEnv;
     a.srgbLut = h->dLut;
     a.tilesX = h->tilesX();

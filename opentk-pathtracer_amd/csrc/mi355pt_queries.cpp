@@ -93,7 +93,7 @@ static void first_hit_args(pt_handle h, pt::FrameArgs &a, int frame_index)
     a.spp = 1;
     a.batchFrames = 1;
     a.frame = frame_index;
-    a.objects = h->dObjects;
+    a.objects = h->dObjects; // (the block AND sphereGeom behind it, pt_kernels.hpp kSphereGeomOffset: `objects` always names an allocation of 26,624 + 4,096 bytes)
     a.tilesX = h->tilesX();
     a.tilesY = h->tilesY();
 }

@@ -72,6 +72,23 @@ PT_DEV ColdArgs cold_args()
     return p;
 }
 
+// Scene geometry as scalar operands (ray_trace_t<SCALAR>): every sphere and cuboid is the same for all 64 lanes, so the loops of the
+// spp = 1 kernels with materials in LDS fetch it with scalar loads from device memory — four spheres = one s_load_dwordx16 from the packed
+// copy behind `objects` (pt_kernels.hpp: kSphereGeomOffset), a cuboid's min / max = one s_load_dwordx8 from the std140 block itself — and
+// use the SGPRs as the one scalar source a VALU instruction may carry.  Same instructions per lane, same bits; only where the operand lives
+// changes.  The tile pass's masked SPHERE loop keeps its LDS
+// reads: one s_load_dwordx4 per surviving sphere (0 - 5 per tile) was built and measured, and on its own it did not lower the kernel time
+// (CHANGELOG.md).
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef float f8v __attribute__((ext_vector_type(8)));
+typedef float f16v __attribute__((ext_vector_type(16)));
+// one scalar load of a T at `byteOffset` (unsigned 32 bits: it travels as the load's SGPR offset, no 64-bit address arithmetic) behind `base`
+template <typename T>
+PT_DEV T cold_load(const float *base, unsigned int byteOffset)
+{
+    return *(const __attribute__((address_space(4))) T *)((const __attribute__((address_space(4))) char *)base + byteOffset);
+}
+
 PT_DEV v3 env_texel(const EnvRef &e, int face, int x, int y)
 {
     size_t idx = ((size_t)face * e.size + (size_t)y) * e.size + (size_t)x;
@@ -266,7 +283,9 @@ PT_DEV Material load_material(const float4 *m)
 #define PT_WALK_ROUNDS 6
 #endif
 
-template <bool MASKED, bool MATLDS, bool GRID = false, bool SHARE = false>
+// SCALAR (rows of the spp = 1 kernels with materials in LDS and no grid): sphere and cuboid geometry arrives through scalar loads (above);
+// the winner section still reads LDS at its per-lane index.
+template <bool MASKED, bool MATLDS, bool GRID = false, bool SHARE = false, bool SCALAR = false>
 PT_DEV bool ray_trace_t(const SceneLds &sc, int ns, int nc, v3 o, v3 d, Hit &h, const unsigned long long *masks, float &walkFrom PROF_PARAM)
 {
     PROF_BEGIN
@@ -413,6 +432,24 @@ PT_DEV bool ray_trace_t(const SceneLds &sc, int ns, int nc, v3 o, v3 d, Hit &h, 
     // multiply-adds that CONSUME the shared products are written as instructions: the compiler's two-address v_fmac would overwrite
     // the product (and then copy it for the next sphere: three moves per sphere); `volatile` keeps them in program order between the
     // run headers.  Four spheres per step as before: four broadcast LDS reads issued together, one exposed LDS latency per step.
+    // One sphere of a four-sphere step of the run loops below, for both homes of the geometry words X, Y, Z, W: CON = "v" (read from LDS) with
+    // SUB = PT_SUB_V, or CON = "s" (scalar load) with SUB = PT_SUB_S — o - c with c as the instruction's scalar source is v_subrev with c in src0.
+#define PT_SUB_V(D, O, C) "v_sub_f32 " D ", " O ", " C
+#define PT_SUB_S(D, O, C) "v_subrev_f32 " D ", " C ", " O
+#define PT_RUN_SPHERE(X, Y, Z, W, K, CON, SUB)                                                                           \
+        if (runs & (1u << (K)))                                                                                          \
+            asm volatile(SUB("%0", "%4", "%6") "\n " SUB("%1", "%5", "%7") "\n v_mul_f32 %2, %8, %0\n v_mul_f32 %3, %0, %0" \
+                         : "=&v"(ocx), "=&v"(ocz), "=&v"(bx), "=&v"(cx)                                                  \
+                         : "v"(o.x), "v"(o.z), CON(X), CON(Z), "v"(d.x)); /* oc.x, oc.z, d.x * oc.x, oc.x * oc.x */       \
+        asm volatile(SUB("%2", "%3", "%4") "\n"     /* oc.y */                                                           \
+                     "v_fma_f32 %0, %5, %2, %6\n"   /* fma(d.y, oc.y, d.x * oc.x) */                                      \
+                     "v_fma_f32 %1, %2, %2, %7\n"   /* fma(oc.y, oc.y, oc.x * oc.x) */                                    \
+                     "v_fma_f32 %0, %8, %9, %0\n"   /* == v_dot(d, oc) */                                                 \
+                     "v_fma_f32 %1, %9, %9, %1"     /* == v_dot(oc, oc) */                                                \
+                     : "=&v"(b[K]), "=&v"(c[K]), "=&v"(ocy)                                                              \
+                     : "v"(o.y), CON(Y), "v"(d.y), "v"(bx), "v"(cx), "v"(d.z), "v"(ocz));                                \
+        c[K] = f_fma(-(W), (W), c[K]);              /* ... - r * r (scalar: one SGPR named twice is one constant-bus read) */ \
+        disc[K] = f_fma(b[K], b[K], -c[K]);
     if constexpr (!SHARE) {
     // the plain loop, four spheres per step: four broadcast LDS reads issued together, one wave-level branch per sphere
         for (; i + 4 <= ns; i += 4) {
@@ -436,26 +473,46 @@ PT_DEV bool ray_trace_t(const SceneLds &sc, int ns, int nc, v3 o, v3 d, Hit &h, 
             float c = f_fma(-s.w, s.w, v_dot(oc, oc));
             candidate(i, b, c, f_fma(b, b, -c));
         }
+    } else if constexpr (SCALAR) {
+        // The run loop below on scalar operands: per step one 16-dword scalar load of spheres i .. i + 3 and one wait, where the LDS form
+        // issues a v_mov of the address, four broadcast ds_read_b128, two waits and the address increment, and holds 16 VGPRs.  The blocks
+        // are the ones of PT_RUN_SPHERE with the geometry word as the instruction's scalar source (v_subrev: o - c with c in src0).
+        if (i < ns) {
+        ColdArgs rca = cold_args();
+        const float *objs = rca->objects; // (re-read here, not held across the bounce)
+        float ocz = 0.0f, bx = 0.0f, cx = 0.0f;
+        const int ns4 = ns & ~3;
+        while (i < ns4) { // (i is a multiple of 32 here)
+            unsigned int runs = ((const __attribute__((address_space(4))) unsigned int *)rca->sphereRunStart)[i >> 5];
+            const int end = ns4 < i + 32 ? ns4 : i + 32;
+            for (; i < end; i += 4) {
+                const f16v q = cold_load<f16v>(objs, (unsigned int)kSphereGeomOffset + 16u * (unsigned int)i);
+                float b[4], c[4], disc[4], ocx, ocy;
+                PT_RUN_SPHERE(q[0], q[1], q[2], q[3], 0, "s", PT_SUB_S)
+                PT_RUN_SPHERE(q[4], q[5], q[6], q[7], 1, "s", PT_SUB_S)
+                PT_RUN_SPHERE(q[8], q[9], q[10], q[11], 2, "s", PT_SUB_S)
+                PT_RUN_SPHERE(q[12], q[13], q[14], q[15], 3, "s", PT_SUB_S)
+                runs >>= 4;
+                asm volatile("" : "+v"(disc[0]), "+v"(disc[1]), "+v"(disc[2]), "+v"(disc[3])); // (the four tests below stay below the four blocks above)
+#pragma unroll
+                for (int k = 0; k < 4; k++) // `any`: see the LDS form below
+                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(disc[k] < 0.0f)) != 0ull, 0)) candidate(i + k, b[k], c[k], disc[k]);
+            }
+        }
+        for (; i < ns; i++) { // (ns % 4 spheres: one s_load_dwordx4 each)
+            const f4v s = cold_load<f4v>(objs, (unsigned int)kSphereGeomOffset + 16u * (unsigned int)i);
+            v3 oc = V(o.x - s[0], o.y - s[1], o.z - s[2]);
+            float b = v_dot(d, oc);
+            float c = f_fma(-s[3], s[3], v_dot(oc, oc));
+            candidate(i, b, c, f_fma(b, b, -c));
+        }
+        }
     } else if (i < ns) {
         // Issue slots, not arithmetic, are what this loop costs (tools/ubench3.hip: a scalar instruction takes an issue slot like a
         // vector one): per sphere ONE asm block (the compiler pads every asm statement with an s_nop), the run bit tested straight
         // from the 32-bit word, and a sphere that no lane can hit costs one compare and one scalar branch (`any`, below).
         ColdArgs rca = cold_args();
         float ocz = 0.0f, bx = 0.0f, cx = 0.0f;
-#define PT_RUN_SPHERE(S, K)                                                                                              \
-        if (runs & (1u << (K)))                                                                                          \
-            asm volatile("v_sub_f32 %0, %4, %6\n v_sub_f32 %1, %5, %7\n v_mul_f32 %2, %8, %0\n v_mul_f32 %3, %0, %0"     \
-                         : "=&v"(ocx), "=&v"(ocz), "=&v"(bx), "=&v"(cx)                                                  \
-                         : "v"(o.x), "v"(o.z), "v"(S.x), "v"(S.z), "v"(d.x)); /* oc.x, oc.z, d.x * oc.x, oc.x * oc.x */  \
-        asm volatile("v_sub_f32 %2, %3, %4\n"       /* oc.y */                                                           \
-                     "v_fma_f32 %0, %5, %2, %6\n"   /* fma(d.y, oc.y, d.x * oc.x) */                                      \
-                     "v_fma_f32 %1, %2, %2, %7\n"   /* fma(oc.y, oc.y, oc.x * oc.x) */                                    \
-                     "v_fma_f32 %0, %8, %9, %0\n"   /* == v_dot(d, oc) */                                                 \
-                     "v_fma_f32 %1, %9, %9, %1"     /* == v_dot(oc, oc) */                                                \
-                     : "=&v"(b[K]), "=&v"(c[K]), "=&v"(ocy)                                                              \
-                     : "v"(o.y), "v"(S.y), "v"(d.y), "v"(bx), "v"(cx), "v"(d.z), "v"(ocz));                              \
-        c[K] = f_fma(-S.w, S.w, c[K]);              /* ... - r * r */                                                    \
-        disc[K] = f_fma(b[K], b[K], -c[K]);
         const int ns4 = ns & ~3;
         while (i < ns4) { // (i is a multiple of 32 here)
             unsigned int runs = ((const __attribute__((address_space(4))) unsigned int *)rca->sphereRunStart)[i >> 5];
@@ -464,10 +521,10 @@ PT_DEV bool ray_trace_t(const SceneLds &sc, int ns, int nc, v3 o, v3 d, Hit &h, 
                 const float4 s0 = sc.sph[i], s1 = sc.sph[i + 1], s2 = sc.sph[i + 2], s3 = sc.sph[i + 3];
                 float b[4], c[4], disc[4], ocx, ocy;
                 asm volatile("" ::"v"(s0.x), "v"(s0.z), "v"(s1.x), "v"(s1.z), "v"(s2.x), "v"(s2.z), "v"(s3.x), "v"(s3.z)); // (whole float4 reads, all four at once)
-                PT_RUN_SPHERE(s0, 0)
-                PT_RUN_SPHERE(s1, 1)
-                PT_RUN_SPHERE(s2, 2)
-                PT_RUN_SPHERE(s3, 3)
+                PT_RUN_SPHERE(s0.x, s0.y, s0.z, s0.w, 0, "v", PT_SUB_V)
+                PT_RUN_SPHERE(s1.x, s1.y, s1.z, s1.w, 1, "v", PT_SUB_V)
+                PT_RUN_SPHERE(s2.x, s2.y, s2.z, s2.w, 2, "v", PT_SUB_V)
+                PT_RUN_SPHERE(s3.x, s3.y, s3.z, s3.w, 3, "v", PT_SUB_V)
                 runs >>= 4;
                 asm volatile("" : "+v"(disc[0]), "+v"(disc[1]), "+v"(disc[2]), "+v"(disc[3])); // (the four tests below stay below the four blocks above)
 #pragma unroll
@@ -476,6 +533,8 @@ PT_DEV bool ray_trace_t(const SceneLds &sc, int ns, int nc, v3 o, v3 d, Hit &h, 
             }
         }
 #undef PT_RUN_SPHERE
+#undef PT_SUB_V
+#undef PT_SUB_S
         for (; i < ns; i++) { // (ns % 4 spheres: evaluated on their own)
             float4 s = sc.sph[i];
             v3 oc = V(o.x - s.x, o.y - s.y, o.z - s.z);
@@ -493,8 +552,22 @@ PT_DEV bool ray_trace_t(const SceneLds &sc, int ns, int nc, v3 o, v3 d, Hit &h, 
     v3 invd = V(f_rcp(d.x), f_rcp(d.y), f_rcp(d.z)); // slab test by reciprocal (pt-f32 contract)
     // MASKED: masks[4] = the cuboids some ray of the wavefront's bundle can reach (cone_cuboid_mask; all ones = not culled: the plain
     // loop); a cuboid outside it fails `t1 <= t2 && t2 > 0` for every lane and never changes T
+    [[maybe_unused]] const float *cobj = nullptr;
+    if constexpr (SCALAR) cobj = cold_args()->objects;
     auto cuboid = [&](int i) {
-        float4 mn = sc.cmin[i], mx = sc.cmax[i];
+        float4 mn, mx;
+        if constexpr (SCALAR) { // (i is wave-uniform: min and max are adjacent float4s, one s_load_dwordx8)
+            unsigned int ui = (unsigned int)i;
+            // (MASKED: i comes from the mask, and left to itself the compiler forms the 64-bit address with a vector multiply-add and two
+            // v_readfirstlane, at three more VGPRs for the kernel; opaque, the product is a scalar multiply and travels as the load's SGPR offset)
+            if constexpr (MASKED) asm("" : "+s"(ui));
+            const f8v q = cold_load<f8v>(cobj, 16u * 1280u + 96u * ui); // Cuboids[] start at float4 index 1280: min, max, material
+            mn = make_float4(q[0], q[1], q[2], q[3]);
+            mx = make_float4(q[4], q[5], q[6], q[7]);
+        } else {
+            mn = sc.cmin[i];
+            mx = sc.cmax[i];
+        }
         v3 t0s = V((mn.x - o.x) * invd.x, (mn.y - o.y) * invd.y, (mn.z - o.z) * invd.z);
         v3 t1s = V((mx.x - o.x) * invd.x, (mx.y - o.y) * invd.y, (mx.z - o.z) * invd.z);
         v3 sm = V(f_min(t0s.x, t1s.x), f_min(t0s.y, t1s.y), f_min(t0s.z, t1s.z));
@@ -816,12 +889,12 @@ PT_DEV float bsdf(v3 &ro, v3 &rd, const Hit &h, bool &isRefractive, uint32_t &se
 // continues (hit, survived Russian roulette), false when it ended (miss -> environment, or roulette kill).
 // GATES: the wave-uniform gates around Beer's law (below).  The spp > 1 kernel with materials in device memory and no grid is at its
 // register limit and pays for them with a scratch reload, so it alone keeps the ungated form.
-template <bool MASKED, bool MATLDS, bool GRID = false, bool SHARE = false, bool GATES = true>
+template <bool MASKED, bool MATLDS, bool GRID = false, bool SHARE = false, bool GATES = true, bool SCALAR = false>
 PT_DEV bool bounce_step_t(const SceneLds &sc, int ns, int nc, const EnvRef &env, v3 &ro, v3 &rd, v3 &throughput, v3 &rad,
                           uint32_t &seed, const unsigned long long *masks, float &walkFrom PROF_PARAM)
 {
     Hit h;
-    const bool hit = ray_trace_t<MASKED, MATLDS, GRID, SHARE>(sc, ns, nc, ro, rd, h, masks, walkFrom PROF_PASS);
+    const bool hit = ray_trace_t<MASKED, MATLDS, GRID, SHARE, SCALAR>(sc, ns, nc, ro, rd, h, masks, walkFrom PROF_PASS);
     if constexpr (GRID) {
         if (walkFrom >= 0.0f) return true; // the walk was cut short (WALK SLICES): the path is unchanged, the caller repeats this bounce
     }

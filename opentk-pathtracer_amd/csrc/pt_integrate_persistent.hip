@@ -686,7 +686,7 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
                         [[maybe_unused]] float4 plast = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                         if (valid) {
                             if (0 < a.rayDepth)
-                                tcont = bounce_step_t<true, MATLDS>(sc, a.numSpheres, a.numCuboids, env, to, td, tthr, trad, tseed, masks, walkFresh PROF_DUMMY);
+                                tcont = bounce_step_t<true, MATLDS, false, false, true, (SPP1 && MATLDS && !GRID)>(sc, a.numSpheres, a.numCuboids, env, to, td, tthr, trad, tseed, masks, walkFresh PROF_DUMMY);
                             if (1 >= a.rayDepth) tcont = false;
                             tkeep = tcont;
                             if constexpr (CARRY) {
@@ -1044,7 +1044,7 @@ __global__ __launch_bounds__(NWAVES * 64, MIN_WAVES_PER_SIMD) void pt_integrate_
             // lane mask that did not fit the scalar registers and came back through two v_readlane per iteration.
             int nsIter = a.numSpheres, ncIter = a.numCuboids;
             asm volatile("" : "+s"(nsIter), "+s"(ncIter));
-            if (trace && bounce < a.rayDepth) cont = bounce_step_t<false, MATLDS, GRID, (MATLDS && !GRID)>(sc, nsIter, ncIter, env, ro, rd, throughput, rad, seed, nullptr, walkFrom PROF_PASS);
+            if (trace && bounce < a.rayDepth) cont = bounce_step_t<false, MATLDS, GRID, (MATLDS && !GRID), true, (MATLDS && !GRID)>(sc, nsIter, ncIter, env, ro, rd, throughput, rad, seed, nullptr, walkFrom PROF_PASS); // (SCALAR: geometry through scalar loads, pt_device.hpp)
             if (trace && !(GRID && walkFrom >= 0.0f)) { // (else: the grid walk of this bounce continues in the next iteration, pt_device.hpp WALK SLICES)
                 bounce++;
                 pending = !cont || bounce >= a.rayDepth;

@@ -26,7 +26,7 @@ struct FrameArgs {
     int rayDepth, spp; // compute.glsl:90-91
     int frame;         // thisRendererFrame (compute.glsl:96)
     int envSize, envFormat; // cube face size; 0 = RGBA32F, 1 = SRGB8_A8
-    const float *objects;   // device copy of the raw 26,624-byte GameObjectsUBO (std140)
+    const float *objects;   // device copy of the raw 26,624-byte GameObjectsUBO (std140); sphereGeom follows it (kSphereGeomOffset, below)
     const void *env;        // device cube: [6][envSize][envSize] texels (float4 or uchar4)
     const float *srgbLut;   // 256-entry sRGB8 -> linear table (device)
     float4 *accum;          // rows x width RGBA32F accumulation image (row 0 = image row y0)
@@ -355,6 +355,27 @@ hipError_t launch_atmosphere(const AtmoArgs &a, hipStream_t stream);
 hipError_t launch_atmosphere_reference(const AtmoArgs &a, hipStream_t stream);
 // masks[kTileMaskWords * tile + w] for every 8x8 tile of the launch described by `a` (tilesX x tilesY tiles; see FrameArgs::tileMasks)
 hipError_t launch_tile_masks(const FrameArgs &a, unsigned long long *masks, hipStream_t stream);
+// Packed sphere geometry (scalar sphere step of ray_trace_t, pt_device.hpp): float4 sphereGeom[kSphereGeomEntries] = (c.x, c.y, c.z, r) of
+// every sphere, a bit copy of bytes 80 i .. 80 i + 15 of the std140 block, stride 16 so that four spheres are one 16-dword scalar load.
+// It lives in the allocation of FrameArgs::objects, kSphereGeomOffset bytes behind its start (a multiple of 64: the allocation is aligned
+// to 256), so a kernel finds it from `objects` with an immediate offset and FrameArgs keeps its layout — it has no 8-byte hole, and growing
+// it would move the second kernel argument of every kernel that has one.
+constexpr int kSphereGeomOffset = 26624; // PT_GAME_OBJECTS_UBO_SIZE
+constexpr int kSphereGeomEntries = 256;  // PT_MAX_SPHERES
+constexpr int kSphereStride = 80;        // bytes of a std140 Sphere (geometry + material)
+static_assert(kSphereGeomOffset % 64 == 0 && kSphereGeomOffset >= kSphereGeomEntries * kSphereStride, "sphereGeom: aligned, behind the block");
+// the spheres whose bytes an upload of [byteOffset, byteOffset + size) touches: [first, first + count), count = 0 when it touches none
+inline void sphere_geom_range(int byteOffset, int size, int &first, int &count)
+{
+    first = count = 0;
+    if (size <= 0 || byteOffset < 0 || byteOffset >= kSphereGeomEntries * kSphereStride) return;
+    first = byteOffset / kSphereStride;
+    long long last = ((long long)byteOffset + size - 1) / kSphereStride;
+    if (last > kSphereGeomEntries - 1) last = kSphereGeomEntries - 1;
+    count = (int)last - first + 1;
+}
+// sphereGeom[first .. first + count) := the geometry words of those spheres in `objects` (both in the allocation of `objects`)
+hipError_t launch_sphere_geom(float *objects, int first, int count, hipStream_t stream);
 hipError_t launch_clear(float4 *p, size_t n, hipStream_t stream);
 // alpha := 1 over n pixels (pt_write_result / pt_bind_result_buffer: alpha is the frame tag inside pipelined launches)
 hipError_t launch_set_alpha(float4 *p, size_t n, hipStream_t stream);

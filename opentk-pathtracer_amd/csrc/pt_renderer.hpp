@@ -78,7 +78,8 @@ struct pt_renderer {
     unsigned char basic[PT_BASIC_DATA_UBO_SIZE] = {0};   // host shadow of UBO 0 (travels as kernel argument)
     unsigned char atmoUbo[PT_ATMOSPHERE_UBO_SIZE] = {0}; // host shadow of UBO 2
 
-    float *dObjects = nullptr;      // 26,624 B device copy of UBO 1
+    float *dObjects = nullptr;      // 26,624 B device copy of UBO 1, and behind it in the same allocation (pt::kSphereGeomOffset) the packed
+                                    // sphere geometry float4 sphereGeom[256] = bytes 80 i .. 80 i + 15 of every sphere, refreshed behind every upload
     // Sphere grid of large scenes (pt_sphere_grid.hpp): rebuilt from a host shadow of UBO 1 before the first launch after the
     // scene or the sphere count changed
     unsigned char objectsShadow[PT_GAME_OBJECTS_UBO_SIZE] = {0};

@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("MI355PT_LIB") or os.path.join(HERE, "libmi355pt.so")  # MI355PT_LIB: A/B tuning builds
 HEADER = os.path.join(REPO, "include", "mi355pt.h")
 SOURCES = ["pt_integrate_persistent.hip", "pt_integrate_multisample.hip", "pt_integrate_reference.hip", "pt_first_hit.hip", "pt_denoise.hip",
-           "pt_denoise_moments.hip", "pt_adaptive.hip", "pt_adaptive_state.hip", "pt_denoise_adaptive.hip", "pt_helper_kernels.hip", "mi355pt.cpp", "mi355pt_launch.cpp", "mi355pt_handover.cpp",
+           "pt_denoise_moments.hip", "pt_adaptive.hip", "pt_adaptive_state.hip", "pt_denoise_adaptive.hip", "pt_helper_kernels.hip", "pt_sphere_geom.hip", "mi355pt.cpp", "mi355pt_launch.cpp", "mi355pt_handover.cpp",
            "mi355pt_present.cpp", "mi355pt_debug.cpp", "mi355pt_queries.cpp", "mi355pt_multi.cpp"]
 # -ffp-contract=off / -fno-fast-math are part of the pt-f32 arithmetic contract (csrc/pt_math.hpp)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-fPIC", "-shared",
